@@ -2,13 +2,21 @@
 """Headline benchmark: images/sec of full training steps (fwd + DFL/QFL loss + bwd + grad sync + AdamW) of the
 `s` preset at 640x640 bf16 on synthetic COCO-shaped batches, 32 images per GPU (BASELINE.json configs[1]/[2]).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `value` = all ranks' images / max-over-ranks time of exactly K steps with the
-inputs resident in HBM.  `roofline` = the dominant kernel group of the step measured live with stream events
-in an instrumented (eager) step: algorithmic FLOPs of those launches / their summed duration vs the dense bf16
-MFMA peak.  `cpu_baseline` (rank 0, N=1 only) = the CPU oracle restatement timed on this box's host cores.
+inputs resident in HBM; `ms_per_step` = that time / K.  A plain run sets up, warms up, times the K steps and
+prints the line: the keys below are null in it.  `--full` adds them (`--no-roofline`, `--no-extra` and
+`--no-cpu-baseline` drop single legs):
+`roofline` = the dominant kernel group of the step measured live with stream events in an instrumented (eager)
+step: algorithmic FLOPs of those launches / their summed duration vs the dense bf16 MFMA peak, with
+`roofline_layerwise`, `roofline_hbm` and `roofline_groups` from the same step.  `config.rccl` (N > 1) = which ranks
+and devices took part in the exchange.  `extra` (rank 0, N=1, preset s) = other presets, precisions and
+configurations.  `cpu_baseline` (rank 0, N=1 only) = the CPU oracle restatement timed on the host cores.
+
+`--dump-outputs DIR` writes what the last timed step computed as float32 DIR/<name>.npy (see `dump_outputs`); the
+inputs (initial weights, batch) are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -21,6 +29,7 @@ for p in (ROOT, os.path.join(ROOT, "custom-yolo-implmentation_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -44,6 +53,54 @@ def synthetic_batch(n, res, nc, seed, device):
         gts.append(torch.cat([torch.rand(m, 2, generator=g) * res, torch.rand(m, 2, generator=g) * (0.4 * res) + 8,
                               torch.randint(0, nc, (m, 1), generator=g).float()], 1))
     return img.to(device), [t.to(device) for t in gts]
+
+
+DUMP_SAMPLE = 1 << 22                 # parameters kept in the dump: 16 MiB, the whole dump stays under 64 MB
+
+
+def seeded_state(model, runner):
+    """The tensors a step reads and updates besides the optimizer's moments, with a copy of their values now."""
+    live = list(model.parameters()) + list(model.buffers())
+    if runner.amp is not None:
+        live += [runner.amp.state, runner.amp.tracker]
+    return live, [t.detach().clone() for t in live]
+
+
+@torch.no_grad()
+def restore_seeded_state(state, opt):
+    live, saved = state
+    for t, s in zip(live, saved):
+        t.copy_(s)
+    for st in opt.state.values():          # moments and step counter back to a fresh optimizer's zeros
+        for v in st.values():
+            if torch.is_tensor(v):
+                v.zero_()
+
+
+def dump_outputs(out_dir, model, scalars):
+    """What the last timed step handed its caller, as float32 .npy files: `loss` = (total, box, cls) of the step, and the
+    model it updated in place: `params` = every parameter after the optimizer update, flattened in `model.parameters()`
+    order (longer than DUMP_SAMPLE -- preset s: 9.5 M -- it keeps the elements at a fixed seeded sample of indices), and
+    `bn_running_stats` = every BatchNorm running mean and variance.
+
+    The default step sums BatchNorm statistics with float atomics, whose order differs from run to run, and AdamW's first
+    updates are close to lr * sign(gradient): over a trajectory of steps the last-bit differences grow into different
+    weights.  So with --dump-outputs the last timed step starts again from the seeded state (initial weights and buffers,
+    fresh optimizer state; restored off the clock) and runs the same captured default step as every other.  Measured on
+    an MI355X (preset s, bf16), two runs then differ by up to 2e-3 relative on `loss`, 2e-5 of the largest value on
+    `params` (elements whose gradient changes sign move by 2 * lr the other way) and 6e-4 of the largest value on
+    `bn_running_stats`.  The gradients themselves are not dumped: at the random initial weights the loss's anchor
+    assignment has near-ties that this noise flips, and they differ by up to 50 % (L2) between two runs."""
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    if flat_p.numel() > DUMP_SAMPLE:
+        idx = torch.randperm(flat_p.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+        flat_p = flat_p[idx.to(flat_p.device)]
+    stats = torch.cat([b.detach().reshape(-1).float() for name, b in model.named_buffers()
+                       if name.endswith(("running_mean", "running_var"))])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("loss", scalars), ("params", flat_p), ("bn_running_stats", stats)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 class KernelTimer:
@@ -435,10 +492,19 @@ def main():
     ap.add_argument("--precision", choices=["bfloat16", "float16", "float32"], default="bfloat16")
     ap.add_argument("--nc", type=int, default=80)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra data points (preset l at 16 images, config-5 NMS)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline legs, config.rccl (N > 1), the extra data points and "
+                         "the CPU baseline (a plain run leaves them null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline legs")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the extra data points (preset l at 16 images, config-5 NMS, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, parameters, gradients, BatchNorm statistics) "
+                         "as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -457,6 +523,7 @@ def main():
         else:
             dist.init_process_group(backend, init_method="env://", world_size=world, rank=rank)
 
+    from src.hipops import functions as F_
     from src.hipops import ops
     from src.model.losses import PackedTargets, YoloDFLQFLoss
     from src.model.model_builder import Model
@@ -481,6 +548,7 @@ def main():
     runner = TrainStepRunner(model, crit, opt, args.precision, use_graph=not args.no_graph,
                              grad_comm_dtype=(None if os.environ.get("BENCH_COMM_DTYPE") == "fp32" else torch.bfloat16)
                              if world > 1 else None)
+    start = seeded_state(model, runner) if args.dump_outputs else None
     runner.capture(img, packed)
 
     for _ in range(args.warmup):
@@ -489,7 +557,13 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if start is not None and i == args.steps - 1:      # the dumped step starts from the seeded state (dump_outputs)
+            torch.cuda.synchronize()
+            paused = time.perf_counter()
+            restore_seeded_state(start, opt)
+            torch.cuda.synchronize()
+            t0 += time.perf_counter() - paused
         loss = runner.step()
     if world > 1:
         dist.barrier()
@@ -502,10 +576,12 @@ def main():
     final_loss = float(loss)
     if rank == 0:
         print(f"[bench] {args.steps} steps in {dt:.4f} s -> {args.batch * world * args.steps / dt:.1f} img/s", file=sys.stderr, flush=True)
+        if args.dump_outputs:            # before the roofline leg: its eager step overwrites gradients and BatchNorm statistics
+            dump_outputs(args.dump_outputs, model, runner.scalars)
 
     # ---- RCCL evidence for the N > 1 line: who took part in the exchange, on which devices, with which buckets
     rccl = None
-    if world > 1:
+    if world > 1 and args.full:
         props = torch.cuda.get_device_properties(dev)
         ident = f"{os.uname().nodename}/{local}/{getattr(props, 'uuid', '') or getattr(props, 'pci_bus_id', '')}"
         idents = [None] * world
@@ -520,9 +596,8 @@ def main():
                     graphs=dict(A=runner.graph is not None, B=runner.graph_b is not None, C=runner.graph2 is not None))
 
     roofline, groups_out, roofline_hbm, roofline_layerwise = None, None, None, None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         timer = KernelTimer(ops).install()
-        from src.hipops import functions as F_
         F_.OVERLAP_WGRAD = False                     # time every leaf alone (in the graph wgrad runs beside dgrad
         two_streams, F_.HEAD_TWO_STREAMS = F_.HEAD_TWO_STREAMS, False      # and the head's class branches beside the box ones)
         del loss                                     # the replayed step's loss node is not kept alive across the eager step
@@ -592,7 +667,7 @@ def main():
     # ---- extra data points observed by the driver (not the metric): BASELINE config 4's model per GPU and config 5's NMS
     extra = None
     hip_graph, opt_in_graph = runner.graph is not None, runner.opt_in_graph
-    if rank == 0 and world == 1 and not args.no_extra and args.preset == "s":
+    if rank == 0 and world == 1 and args.full and not args.no_extra and args.preset == "s":
         del runner, opt, model, packed
         torch.cuda.empty_cache()
         extra = {}
@@ -609,7 +684,7 @@ def main():
             extra["error"] = repr(e)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle.train_step import time_cpu_nms, time_cpu_steps
         # launched like slurm/distributed_training_cpu.sbatch:87-91: one rank, gloo, DDP gradient averaging, all host threads
         # (the reference's thread rule for one rank = torch's default = every host core; on a many-core box that
@@ -637,7 +712,8 @@ def main():
                    config=dict(workload=f"preset {args.preset} (width {PRESETS[args.preset]['width'][1]}..{PRESETS[args.preset]['width'][5]}, depth {PRESETS[args.preset]['depth'][0]}) {args.res}x{args.res} train step "
                                         f"(fwd+DFL/QFL loss+bwd+grad sync+AdamW), COCO-80 synthetic, {args.batch} img/GPU",
                                global_batch=gb, parallelism=f"dp{world}", hip_graph=hip_graph,
-                               optimizer_in_graph=opt_in_graph, final_loss=round(final_loss, 5), rccl=rccl),
+                               optimizer_in_graph=opt_in_graph, deterministic_mode=F_.deterministic_stats(),
+                               final_loss=round(final_loss, 5), rccl=rccl),
                    roofline=roofline, roofline_layerwise=roofline_layerwise, roofline_hbm=roofline_hbm,
                    roofline_groups=groups_out, cpu_baseline=cpu, extra=extra)
         print(json.dumps(out), flush=True)

@@ -49,11 +49,11 @@ Raw sums:
 """)
 open(os.path.join(P, PRE + "_summary.md"), "w").write(f"""# {ROUND} (final state) — rocprofv3 summary, MI355X, preset s @640 bf16, 32 img, graph-captured train step
 
-Produced by `bash tools/final_profile.sh` on one MI355X box and `python tools/publish_profile.py`: the default `python3 bench.py`
+Produced by `bash tools/final_profile.sh` on one MI355X box and `python tools/publish_profile.py`: the `python3 bench.py --full`
 line (`profiles/{PRE}_bench.json`: {b['value']:.0f} img/s, {b['ms_per_step']:.2f} ms/step; dominant MFMA kernel group conv fwd+dgrad
 {r['achieved']:.0f} TFLOP/s = {r['frac']:.3f} of 2.5 PF over {r['launches']} leaf calls, {r['avg_launch_us']:.1f} us average), then
 
-    rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra
+    rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra
 
 whose per-kernel statistics are `profiles/{PRE}_kernel_stats.csv` (whole run: capture warm-up, 25 replays, the instrumented
 eager step of the roofline leg).  rocprofv3's average over the conv fwd+dgrad kernels INSIDE the replayed step (k_conv_mfma +
