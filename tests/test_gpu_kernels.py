@@ -1,6 +1,8 @@
 """-m gpu: every HIP leaf (C-ABI entry point) against its plain-torch stand-in on the same seeded inputs.
 
-Tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
+The convolution family (dense, stem, depthwise; forward, data and weight gradients, fused inference epilogues) is held to
+the derived per-element bound of tests/strict_compare.py against a float64 reference.  The other leaves keep check():
+tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
 and round once, the stand-in does the same from the same rounded inputs, so 2 output ulps
 (bf16: 2^-7, f16: 2^-10 relative) of the tensor's max magnitude.  Integer outputs (pool argmax,
 assignment, NMS rows) exact."""
@@ -8,6 +10,7 @@ import pytest
 import torch
 
 import emulated_ops as emu
+import strict_compare as sc
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +55,17 @@ def dev(t, pad_c=0):
     view = buf[:, off:off + c]
     view.copy_(t.to(DEV))
     return view
+
+
+@pytest.fixture(autouse=True, scope="module")
+def _print_observed_maxima():
+    yield
+    print("\n" + sc.report())
+
+
+def old_tol(ref, dtype, mult=1.0):
+    """check()'s limit for this reference: passed to the strict comparator only as the guard 'nowhere wider than before'"""
+    return TOL[dtype] * mult * max(float(ref.abs().max()), 1e-6)
 
 
 def check(got, want, dtype, what, scale=None, mult=1.0):
@@ -149,21 +163,25 @@ def test_conv_fwd_dgrad_wgrad(case, dtype, algo, monkeypatch):
     x = nhwc(rnd(n, cin, h, w, seed=10).to(dtype), pad_c)
     wt = rnd(cout, cin, k, k, seed=11, scale=(cin * k * k) ** -0.5)
     bias = rnd(cout, seed=12)
+    wq = wt.to(dtype)                                     # the weights as the kernels see them
+    fam = "fp32" if dtype == torch.float32 else "generic" if algo == 1 else "auto"
     # forward (+bias)
-    y_ref = emu.conv_fwd(x, emu.pack_weights(wt, k, s, 0, dtype), bias, cout, k, s)
+    y_ref, y_mass = sc.conv_ref(x, wq, k, s)
+    b64 = bias.double().view(1, -1, 1, 1)
+    y_ref, y_mass = y_ref + b64, y_mass + b64.abs()
     y = o.conv_fwd(dev(x), o.pack_weights(wt.to(DEV), k, s, 0, dtype), bias.to(DEV), cout, k, s)
-    check(y, y_ref, dtype, "conv_fwd")
+    sc.assert_close(y, y_ref, y_mass, dtype, f"conv_fwd {case}", fam, old_abs=old_tol(y_ref, dtype))
     # dgrad
     oh, ow = y_ref.shape[2:]
     dy = nhwc(rnd(n, cout, oh, ow, seed=13).to(dtype), pad_c)
     if cin >= 8:
-        dx_ref = emu.conv_dgrad(dy, emu.pack_weights(wt, k, s, 1, dtype), cin, h, w, k, s)
+        dx_ref, dx_mass = sc.dgrad_ref(dy, wq, (n, cin, h, w), k, s)
         dx = o.conv_dgrad(dev(dy), o.pack_weights(wt.to(DEV), k, s, 1, dtype), cin, h, w, k, s)
-        check(dx, dx_ref, dtype, "conv_dgrad")
-    # wgrad (fp32 accumulation over n*oh*ow products; atomics => order noise)
-    dw_ref = emu.conv_wgrad(x, dy, k, s, torch.float32)
+        sc.assert_close(dx, dx_ref, dx_mass, dtype, f"conv_dgrad {case}", fam, old_abs=old_tol(dx_ref, dtype))
+    # wgrad (fp32 accumulation over n*oh*ow products; the generic kernels use atomics => order noise)
+    dw_ref, dw_mass = sc.wgrad_ref(x, dy, (cout, cin, k, k), k, s)
     dw = o.conv_wgrad(dev(x), dev(dy), k, s, torch.float32)
-    check(dw, dw_ref, torch.float32, "conv_wgrad", mult=4.0)
+    sc.assert_close(dw, dw_ref, dw_mass, torch.float32, f"conv_wgrad {case}", fam + "_wgrad", old_abs=old_tol(dw_ref, torch.float32, 4.0))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
@@ -177,11 +195,14 @@ def test_stem_unfold_path(dtype, h, w):
     assert torch.equal(col.cpu(), col_ref)
     y = o.conv_fwd(col, o.stem_pack_weights(wt.to(DEV), dtype), None, 16, 1, 1)
     y_ref = emu.conv_fwd(nhwc(torch.as_tensor(img).to(dtype)), emu.pack_weights(wt, 3, 2, 0, dtype), None, 16, 3, 2)
-    check(y, y_ref, dtype, "stem forward == 3x3/2 conv")
+    y64, y_mass = sc.conv_ref(img.to(dtype), wt.to(dtype), 3, 2)
+    fam = "fp32" if dtype == torch.float32 else "stem"
+    sc.assert_close(y, y64, y_mass, dtype, "stem forward == 3x3/2 conv", fam, old_abs=old_tol(y_ref.double(), dtype))
     dy = nhwc(rnd(*y_ref.shape, seed=17).to(dtype))
     dw = o.stem_unpack_wgrad(o.conv_wgrad(col, dev(dy), 1, 1, torch.float32), torch.float32)
     dw_ref = emu.conv_wgrad(nhwc(img.to(dtype)), dy, 3, 2, torch.float32)
-    check(dw, dw_ref, torch.float32, "stem wgrad", mult=4.0)
+    dw64, dw_mass = sc.wgrad_ref(img.to(dtype), dy, (16, 3, 3, 3), 3, 2)
+    sc.assert_close(dw, dw64, dw_mass, torch.float32, "stem wgrad", fam + "_wgrad", old_abs=old_tol(dw_ref.double(), torch.float32, 4.0))
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -199,8 +220,8 @@ def test_stem_fused_conv(dtype, cout, h, w):
     col = o.stem_im2col(img.to(DEV), dtype)
     acc2 = o.bn_acc_new(cout, DEV)
     y2 = o.conv_fwd(col, wp, None, cout, 1, 1, acc2)
-    y_ref = emu.conv_fwd(nhwc(img.to(dtype)), emu.pack_weights(wt, 3, 2, 0, dtype), None, cout, 3, 2)
-    check(y, y_ref, dtype, "fused stem == 3x3/2 conv")
+    y_ref, y_mass = sc.conv_ref(img.to(dtype), wt.to(dtype), 3, 2)
+    sc.assert_close(y, y_ref, y_mass, dtype, "fused stem == 3x3/2 conv", "stem", old_abs=old_tol(y_ref, dtype))
     assert torch.equal(y.cpu(), y2.cpu()), "fused stem differs from the unfold path"
     st = acc.view(o.BN_REPL, 2, cout).sum(0).cpu()
     yf = y.float().cpu()
@@ -215,14 +236,18 @@ def test_conv_dgrad_with_two_accumulate_sources(dtype, n, cin, cout, h, w, k):
     """dx = dgrad + dx + acc2 in one epilogue == the three terms summed in fp32 and rounded once; the shapes reach the halo,
     ring, gather and generic kernels; dx and acc2 are channel slices of wider buffers (as in C3K2's concat gradient)"""
     o = ops()
-    dy = dev(nhwc(rnd(n, cout, h, w, seed=80).to(dtype)))
     wt = rnd(cout, cin, k, k, seed=81, scale=0.1)
     wb = o.pack_weights(wt.to(DEV), k, 1, 1, dtype)
-    dx0, a2 = nhwc(rnd(n, cin, h, w, seed=82).to(dtype), 16), nhwc(rnd(n, cin, h, w, seed=83).to(dtype), 32)
-    plain = o.conv_dgrad(dy, wb, cin, h, w, k, 1).float().cpu()
-    want = (plain + dx0.float() + a2.float()).to(dtype)
+    bases = min(n, 3)                                     # 32 images: three bases, every image compared
+    pat = sc.image_pattern(n, 80)
+    dyb, dx0b, a2b = (rnd(bases, c_, h, w, seed=sd).to(dtype) for c_, sd in ((cout, 80), (cin, 82), (cin, 83)))
+    dy = dev(nhwc(dyb[pat]))
+    dx0, a2 = nhwc(dx0b[pat], 16), nhwc(a2b[pat], 32)
+    want, mass = sc.dgrad_ref(dyb, wt.to(dtype), (bases, cin, h, w), k, 1)
+    want, mass = want + dx0b.double() + a2b.double(), mass + dx0b.double().abs() + a2b.double().abs()
     got = o.conv_dgrad(dy, wb, cin, h, w, k, 1, acc_into=dev(dx0), acc2=dev(a2))
-    check(got, want, dtype, "dgrad + dst + acc2", mult=2.0)
+    sc.assert_close(got, want, mass, dtype, "dgrad + dst + acc2", "fp32" if dtype == torch.float32 else "auto", pattern=pat,
+                    old_abs=old_tol(want, dtype, 2.0))
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -240,8 +265,8 @@ def test_stem_fused_wgrad(dtype, cout, h, w, pad):
     dw_unf = o.stem_unpack_wgrad(o.conv_wgrad(col, dev(dy), 1, 1, torch.float32), torch.float32)
     scale = float(dw_unf.abs().max())
     assert float((dw - dw_unf).abs().max()) <= 2e-4 * scale, ((dw - dw_unf).abs().max(), scale)
-    dw_ref = emu.conv_wgrad(nhwc(img.to(dtype)), dy, 3, 2, torch.float32)
-    check(dw, dw_ref, torch.float32, "fused stem wgrad", mult=4.0)
+    dw_ref, dw_mass = sc.wgrad_ref(img.to(dtype), dy, (cout, 3, 3, 3), 3, 2)
+    sc.assert_close(dw, dw_ref, dw_mass, torch.float32, "fused stem wgrad", "stem_wgrad", old_abs=old_tol(dw_ref, torch.float32, 4.0))
     dwb = o.stem_wgrad(img.to(DEV), dev(dy), torch.bfloat16)
     assert dwb.dtype == torch.bfloat16 and torch.equal(dwb.float().cpu(), dw.cpu().to(torch.bfloat16).float())
 
@@ -254,18 +279,24 @@ def test_depthwise(dtype, c, h, w):
     o = ops()
     x, dy = nhwc(rnd(2, c, h, w, seed=20).to(dtype)), nhwc(rnd(2, c, h, w, seed=21).to(dtype), 16)   # dy: slice of a wider buffer
     w9 = rnd(c, 9, seed=22, scale=0.3)
-    check(o.dw_fwd(dev(x), w9.to(DEV)), emu.dw_fwd(x, w9), dtype, "dw_fwd")
+    w4 = w9.view(c, 1, 3, 3)
+    y_ref, y_mass = sc.conv_ref(x, w4, 3, 1, groups=c)
+    sc.assert_close(o.dw_fwd(dev(x), w9.to(DEV)), y_ref, y_mass, dtype, "dw_fwd", "depthwise", old_abs=old_tol(y_ref, dtype))
     acc = o.bn_acc_new(c, DEV)                                   # forward with the BatchNorm statistics in its epilogue
     ys = o.dw_fwd(dev(x), w9.to(DEV), acc)
     assert torch.equal(ys.cpu(), o.dw_fwd(dev(x), w9.to(DEV)).cpu())
     st, yf = acc.view(o.BN_REPL, 2, c).sum(0).cpu(), ys.float().cpu()
     want = torch.stack([yf.sum((0, 2, 3)), (yf * yf).sum((0, 2, 3))])
     assert torch.allclose(st, want, rtol=2e-4, atol=1e-3 * float(want.abs().max())), (st - want).abs().max()
-    check(o.dw_dgrad(dev(dy), w9.to(DEV)), emu.dw_dgrad(dy, w9), dtype, "dw_dgrad")
+    dx_ref, dx_mass = sc.dgrad_ref(dy, w4, (2, c, h, w), 3, 1, groups=c)
+    sc.assert_close(o.dw_dgrad(dev(dy), w9.to(DEV)), dx_ref, dx_mass, dtype, "dw_dgrad", "depthwise", old_abs=old_tol(dx_ref, dtype))
     prev = nhwc(rnd(2, c, h, w, seed=23).to(dtype))
     got = o.dw_dgrad(dev(dy), w9.to(DEV), acc_into=dev(prev).clone(memory_format=torch.preserve_format))
-    check(got, (emu.dw_dgrad(dy, w9).float() + prev.float()).to(dtype), dtype, "dw_dgrad accumulate", mult=2.0)
-    check(o.dw_wgrad(dev(x), dev(dy)), emu.dw_wgrad(x, dy), torch.float32, "dw_wgrad", mult=4.0)
+    want, mass = dx_ref + prev.double(), dx_mass + prev.double().abs()
+    sc.assert_close(got, want, mass, dtype, "dw_dgrad accumulate", "depthwise", old_abs=old_tol(want, dtype, 2.0))
+    dw_ref, dw_mass = sc.wgrad_ref(x, dy, (c, 1, 3, 3), 3, 1, groups=c)
+    sc.assert_close(o.dw_wgrad(dev(x), dev(dy)), dw_ref, dw_mass, torch.float32, "dw_wgrad", "depthwise_wgrad",
+                    old_abs=old_tol(dw_ref, torch.float32, 4.0))
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -276,11 +307,16 @@ def test_fused_inference_depthwise_bias_silu(dtype, c, h, w):
     o = ops()
     x = nhwc(rnd(2, c, h, w, seed=24).to(dtype))
     w9, bias = rnd(c, 9, seed=25, scale=0.3), rnd(c, seed=26, scale=0.5)
-    ref = torch.nn.functional.conv2d(x.float(), w9.view(c, 1, 3, 3), bias, 1, 1, groups=c)
+    v, vmass = sc.conv_ref(x, w9.view(c, 1, 3, 3), 3, 1, groups=c)
+    b64 = bias.double().view(1, -1, 1, 1)
+    v, vmass = v + b64, vmass + b64.abs()
+    sy, smass, e_act = sc.silu_terms(v, vmass)
     for act in (1, 0):
         got = o.dw_fwd_act(dev(x), w9.to(DEV), bias.to(DEV), act)
         assert got is not None
-        check(got, torch.nn.functional.silu(ref) if act else ref, dtype, f"dw_fwd_act act={act}", mult=2.0)
+        ref, mass = (sy, smass) if act else (v, vmass)
+        sc.assert_close(got, ref, mass, dtype, f"dw_fwd_act act={act}", "depthwise", e_act=e_act if act else None,
+                        old_abs=old_tol(ref, dtype, 2.0))
     x12 = nhwc(rnd(2, 12, 5, 6, seed=27).to(dtype))
     assert o.dw_fwd_act(dev(x12), rnd(12, 9, seed=28).to(DEV), rnd(12, seed=29).to(DEV), 1) is None
 
@@ -332,7 +368,8 @@ def test_bn_accumulator_path_with_conv_epilogue_stats(dtype, cin, cout, h, w, k,
     ref_f, ref_b = torch.zeros(8 * 2 * cout), torch.zeros(8 * 2 * cout)
     y = o.conv_fwd(dev(x), o.pack_weights(wt.to(DEV), k, s, 0, dtype), None, cout, k, s, acc_f)
     y_ref = emu.conv_fwd(x, emu.pack_weights(wt, k, s, 0, dtype), None, cout, k, s, ref_f)
-    check(y, y_ref, dtype, "conv y")
+    y64, y_mass = sc.conv_ref(x, wt.to(dtype), k, s)
+    sc.assert_close(y, y64, y_mass, dtype, "conv y", "fp32" if dtype == torch.float32 else "auto", old_abs=old_tol(y64, dtype))
     # statistics of the STORED values: compare with sums of the GPU's own y (isolates the epilogue reduction)
     yf = y.float().cpu()
     sums = acc_f.view(8, 2, cout).sum(0).cpu()
@@ -441,15 +478,19 @@ def test_fused_inference_conv_bias_silu_residual(dtype, cin, cout, h, w, k, s):
     oh, ow = o.conv_out_hw(h, w, k, s)
     res = nhwc(rnd(n, cout, oh, ow, seed=83).to(dtype), 16)
     wp = o.pack_weights(wt.to(DEV), k, s, 0, dtype)
-    ref_y = torch.nn.functional.conv2d(x.float(), wt.to(dtype).float(), bias, s, k // 2)
+    v, vmass = sc.conv_ref(x, wt.to(dtype), k, s)
+    b64 = bias.double().view(1, -1, 1, 1)
+    v, vmass = v + b64, vmass + b64.abs()
+    sy, smass, e_act = sc.silu_terms(v, vmass)
     for act in (1, 0):
         for r in (None, res):
             got = o.conv_fwd_act(dev(x), wp, bias.to(DEV), cout, k, s, act, None if r is None else dev(r))
             assert got is not None, "no MFMA kernel took this shape"
-            want = torch.nn.functional.silu(ref_y) if act else ref_y
+            want, mass = (sy, smass) if act else (v, vmass)
             if r is not None:
-                want = want + r.float()
-            check(got, want, dtype, f"conv_fwd_act act={act} res={r is not None}", mult=2.0)
+                want, mass = want + r.double(), mass + r.double().abs()
+            sc.assert_close(got, want, mass, dtype, f"conv_fwd_act act={act} res={r is not None}", "auto", e_act=e_act if act else None,
+                            old_abs=old_tol(want, dtype, 2.0))
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -464,10 +505,15 @@ def test_fused_inference_stem_bias_silu(dtype, cout, h, w):
     wt = rnd(cout, 3, 3, 3, seed=85, scale=0.2)
     bias = rnd(cout, seed=86, scale=0.5)
     wp = o.stem_pack_weights(wt.to(DEV), dtype)
-    ref = torch.nn.functional.conv2d(img.to(dtype).float(), wt.to(dtype).float(), bias, 2, 1)
+    v, vmass = sc.conv_ref(img.to(dtype), wt.to(dtype), 3, 2)
+    b64 = bias.double().view(1, -1, 1, 1)
+    v, vmass = v + b64, vmass + b64.abs()
+    sy, smass, e_act = sc.silu_terms(v, vmass)
     for act in (1, 0):
         got = o.stem_conv_fwd(img.to(DEV), wp, cout, dtype, None, bias.to(DEV), act)
-        check(got, torch.nn.functional.silu(ref) if act else ref, dtype, f"fused stem act={act}", mult=2.0)
+        ref, mass = (sy, smass) if act else (v, vmass)
+        sc.assert_close(got, ref, mass, dtype, f"fused stem act={act}", "stem", e_act=e_act if act else None,
+                        old_abs=old_tol(ref, dtype, 2.0))
     with pytest.raises(Exception):
         o.stem_conv_fwd(img.to(DEV), wp, cout, dtype, o.bn_acc_new(cout, DEV), bias.to(DEV), 1)
 
