@@ -1,15 +1,19 @@
 """-m gpu: every HIP leaf (C-ABI entry point) against its plain-torch stand-in on the same seeded inputs.
 
 The convolution family (dense, stem, depthwise; forward, data and weight gradients, fused inference epilogues) is held to
-the derived per-element bound of tests/strict_compare.py against a float64 reference.  The other leaves keep check():
+the derived per-element bound of tests/strict_compare.py against a float64 reference, attention (every route, its stash
+and its three gradients) to that of tests/strict_attention.py.  The other leaves keep check():
 tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
 and round once, the stand-in does the same from the same rounded inputs, so 2 output ulps
 (bf16: 2^-7, f16: 2^-10 relative) of the tensor's max magnitude.  Integer outputs (pool argmax,
 assignment, NMS rows) exact."""
+import os
+
 import pytest
 import torch
 
 import emulated_ops as emu
+import strict_attention as sa
 import strict_compare as sc
 from conftest import load_golden
 
@@ -412,52 +416,180 @@ def test_maxpool5_and_upsample(dtype):
 
 
 # ------------------------------------------------------------------------------------------ attention
+# Held to the derived per-element bound of tests/strict_attention.py against float64 references (o, the stash, dQ, dK and
+# dV each under its own family), on top of the check() calls against the autograd stand-in, which stay as the end-to-end
+# anchor.  Routes: 16-bit with dk 32 / dh 64 and <= 448 tokens the fused flash-style kernels (stash: fp32 row
+# log-sum-exp); other 16-bit problems the batched-GEMM route (stash: the probabilities); fp32 the VALU route (stash: row
+# log-sum-exp); attn_fwd_nograd beyond 448 tokens the key-blocked kernel.
+def _route_of(stash, n, heads, t, dtype):
+    if dtype == torch.float32:
+        return "fp32"
+    return "fused" if stash.numel() == n * heads * t * 4 else "gemm"
+
+
+def _stash_views(route, stash, b, t, dtype):
+    """-> (lse (B, T, 1) or None, P (B, T, T) or None); the GEMM route's pad columns (T .. round32(T)) must be zero"""
+    if route != "gemm":
+        return stash.view(torch.float32).reshape(b, t, 1).cpu().double(), None
+    tp = (t + 31) // 32 * 32
+    pm = stash.view(dtype).reshape(b, t, tp).cpu()
+    assert not bool(pm[..., t:].any()), "stashed P: pad columns not zero"
+    return None, pm[..., :t].double()
+
+
+def _attention_case(dtype, heads, dk, dh, qkv_cpu, want_route=None, pad=0, what="attn"):
+    """forward, stash and backward of one batch through the strict comparator and the autograd anchor; everything runs
+    twice and must repeat bit for bit (no route uses atomics).  pad: qkv, d_o and d_vp are channel slices of buffers that
+    many channels wider."""
+    o = ops()
+    n, _, h, w = qkv_cpu.shape
+    t, b, scale = h * w, n * heads, dk ** -0.5
+    qkv = nhwc(qkv_cpu, pad)
+    og, vg, stash = o.attn_fwd(dev(qkv), heads, dk, dh, scale)
+    route = _route_of(stash, n, heads, t, dtype)
+    if want_route is not None and os.environ.get("YOLO_ATTN_FUSED", "1") != "0":
+        assert route == want_route, (route, want_route)
+    q, k, v = sa.split_qkv(qkv_cpu, heads, dk, dh)
+    lse, pm = _stash_views(route, stash, b, t, dtype)
+    o_st = sa.split(og, heads)
+    sa.check_forward(route, q, k, v, scale, dtype, o_st, got_lse=lse, got_p=pm, what=f"{what} [{route}]")
+    o_ref, v_ref, lse_ref = emu.attn_fwd(qkv, heads, dk, dh, scale)
+    check(og, o_ref, dtype, "attn o", mult=2.0)
+    if route != "gemm":
+        check(stash.view(torch.float32), lse_ref, torch.float32, "lse", mult=4.0)
+    assert torch.equal(vg.cpu(), v_ref)
+    og2, vg2, stash2 = o.attn_fwd(dev(qkv), heads, dk, dh, scale)
+    assert torch.equal(og, og2) and torch.equal(vg, vg2) and torch.equal(stash, stash2), "forward does not repeat bit for bit"
+
+    d_o, d_v = nhwc(rnd(n, heads * dh, h, w, seed=51).to(dtype), pad), nhwc(rnd(n, heads * dh, h, w, seed=52).to(dtype), pad)
+    do64, dv64 = sa.split(d_o, heads), sa.split(d_v, heads)
+    dq_ref = None
+    for gv, gv64, tag in ((d_v, dv64, ""), (None, None, " (d_vp None)")):    # None: no gradient through the re-gathered v
+        dq = o.attn_bwd(dev(qkv), og, dev(d_o), dev(gv), stash, heads, dk, dh, scale)
+        sa.check_backward(route, q, k, v, do64, gv64, scale, dtype, *sa.split_qkv(dq, heads, dk, dh), o=o_st, lse=lse, p_stash=pm,
+                          what=f"{what} [{route}]{tag}")
+        check(dq, emu.attn_bwd(qkv, o_ref, d_o, gv, lse_ref, heads, dk, dh, scale), dtype, "attn dqkv" + tag, mult=4.0)
+        assert torch.equal(dq, o.attn_bwd(dev(qkv), og, dev(d_o), dev(gv), stash, heads, dk, dh, scale)), \
+            "backward does not repeat bit for bit"
+    return route
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("heads,dk,dh,h,w", [(2, 32, 64, 6, 6), (4, 32, 64, 20, 20), (1, 16, 32, 13, 11), (3, 32, 64, 10, 19),
                                              (1, 32, 64, 21, 21), (2, 32, 64, 23, 23)])
 def test_attention(dtype, heads, dk, dh, h, w):
     """16-bit with dk 32 / dh 64 and <= 448 tokens: the fused flash-style kernels (36, 190, 400, 441 tokens = every tile-pair
-    count, partial last tiles and query blocks); 529 tokens and the 16 / 32 head: the batched-GEMM route; fp32: the VALU route"""
+    count, partial last tiles and query blocks); 529 tokens and the 16 / 32 head: the batched-GEMM route; fp32: the VALU
+    route.  Every route stashes for its backward and the stash is compared: the fused and fp32 routes the fp32 row
+    log-sum-exp, the GEMM route the 16-bit probabilities."""
+    _attention_case(dtype, heads, dk, dh, rnd(2, heads * (2 * dk + dh), h, w, seed=50).to(dtype))
+
+
+FUSED_T = [1, 15, 16, 17, 128, 129, 224, 225, 256, 257, 400, 416, 417, 441, 448]
+GEMM_CASES = [(16, 32, t) for t in (143, 417, 448, 449, 529)] + [(32, 64, 449), (32, 64, 529)]
+
+
+def _heads_for(t):
+    """3 or 4 heads from 400 tokens on (an image or head mix-up shows), 1 .. 4 below"""
+    return (4 if t % 2 == 0 else 3) if t >= 400 else 1 + t % 4
+
+
+@pytest.mark.parametrize("cls", sa.CLASSES)
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("t", FUSED_T)
+def test_attention_fused_route_lengths(t, dtype, cls):
+    """the fused kernels at every boundary of npair_for() (128 / 129, 224 / 225, 416 / 417, 448), at 256 / 257 where
+    blocking() goes from one workgroup of 16 waves to two of 9, below and around one 16-token tile, on three distinct
+    images; 'negative' (every score below zero) is the class on which one unmasked padded key shows."""
+    heads = _heads_for(t)
+    _attention_case(dtype, heads, 32, 64, sa.make_qkv(3, heads, 32, 64, t, cls, 60 + t, dtype), "fused", what=f"T={t} {cls}")
+
+
+@pytest.mark.parametrize("cls", sa.CLASSES)
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("dk,dh,t", GEMM_CASES)
+def test_attention_gemm_route_lengths(dk, dh, t, dtype, cls):
+    """the batched-GEMM route with its stashed probabilities and its backward: the 16 / 32 head at 143 tokens and on
+    both sides of the step from the register softmax kernels (rows of up to 448 padded columns: 417, 448) to the looped
+    form (449 -> 480 columns, 529); the 32 / 64 head where the fused kernels stop (449, 529)"""
+    heads = 2 if dk == 32 else 3
+    _attention_case(dtype, heads, dk, dh, sa.make_qkv(3, heads, dk, dh, t, cls, 70 + t, dtype), "gemm", what=f"T={t} {cls}")
+
+
+@pytest.mark.parametrize("cls", sa.CLASSES)
+@pytest.mark.parametrize("t", [127, 128, 129, 400])
+def test_attention_fp32_route_lengths(t, cls):
+    """the fp32 VALU route around its 128-row chunk"""
+    heads = 3 if t == 400 else 2
+    _attention_case(torch.float32, heads, 32, 64, sa.make_qkv(3, heads, 32, 64, t, cls, 80 + t, torch.float32), "fp32", what=f"T={t} {cls}")
+
+
+@pytest.mark.parametrize("dtype,dk,dh,t,route", [(torch.bfloat16, 32, 64, 400, "fused"), (torch.float16, 32, 64, 129, "fused"),
+                                                 (torch.bfloat16, 16, 32, 143, "gemm"), (torch.float16, 32, 64, 449, "gemm"),
+                                                 (torch.float32, 32, 64, 129, "fp32")])
+def test_attention_on_channel_slices_of_wider_buffers(dtype, dk, dh, t, route):
+    """qkv, d_o and d_vp with a leading dimension 16 channels beyond their own (the 16-byte alignment holds)"""
+    _attention_case(dtype, 3, dk, dh, sa.make_qkv(3, 3, dk, dh, t, "sharp", 90 + t, dtype), route, pad=16, what=f"T={t} ld = C + 16")
+
+
+def _nograd_case(dtype, heads, base_cpu, pattern, pad=0, what="attn (no stash)"):
+    """attn_fwd_nograd on the batch base_cpu[pattern]: every image and head against the float64 reference of its base"""
     o = ops()
-    n = 2
-    qkv = nhwc(rnd(n, heads * (2 * dk + dh), h, w, seed=50).to(dtype))
+    dk, dh = 32, 64
+    qkv_cpu = base_cpu[list(pattern)]
+    n, _, h, w = qkv_cpu.shape
     scale = dk ** -0.5
-    og, vg, stash = o.attn_fwd(dev(qkv), heads, dk, dh, scale)
-    o_ref, v_ref, lse_ref = emu.attn_fwd(qkv, heads, dk, dh, scale)
-    check(og, o_ref, dtype, "attn o", mult=2.0)
-    if dtype == torch.float32:          # fp32 path stashes the row log-sum-exp, 16-bit paths the probabilities
-        check(stash.view(torch.float32), lse_ref, torch.float32, "lse", mult=4.0)
-    assert torch.equal(vg.cpu(), v_ref)
-    d_o, d_v = nhwc(rnd(n, heads * dh, h, w, seed=51).to(dtype)), nhwc(rnd(n, heads * dh, h, w, seed=52).to(dtype))
-    dq = o.attn_bwd(dev(qkv), og, dev(d_o), dev(d_v), stash, heads, dk, dh, scale)
-    dq_ref = emu.attn_bwd(qkv, o_ref, d_o, d_v, lse_ref, heads, dk, dh, scale)
-    check(dq, dq_ref, dtype, "attn dqkv", mult=4.0)
-    dq0 = o.attn_bwd(dev(qkv), og, dev(d_o), None, stash, heads, dk, dh, scale)          # no gradient through the re-gathered v
-    check(dq0, emu.attn_bwd(qkv, o_ref, d_o, None, lse_ref, heads, dk, dh, scale), dtype, "attn dqkv (d_vp None)", mult=4.0)
+    qkv = nhwc(qkv_cpu, pad)
+    got = o.attn_fwd_nograd(dev(qkv), heads, dk, dh, scale)
+    if dtype == torch.float32:
+        assert got is None
+        return
+    route = "fused" if h * w <= 448 else "long"
+    sa.check_forward(route, *sa.split_qkv(base_cpu, heads, dk, dh), scale, dtype, sa.split(got[0], heads),
+                     pattern=sa.head_pattern(pattern, heads), what=f"{what} [{route}]")
+    o_ref, v_ref, _ = emu.attn_fwd(qkv, heads, dk, dh, scale)
+    check(got[0], o_ref, dtype, "attn o (no stash)", mult=2.0)
+    assert torch.equal(got[1].cpu(), v_ref)
+    again = o.attn_fwd_nograd(dev(qkv), heads, dk, dh, scale)
+    assert torch.equal(got[0], again[0]) and torch.equal(got[1], again[1]), "forward does not repeat bit for bit"
+    if h * w <= 448:                                  # the same kernel as the stashing forward: identical output
+        assert torch.equal(got[0], o.attn_fwd(dev(qkv), heads, dk, dh, scale)[0])
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
 @pytest.mark.parametrize("heads,h,w", [(2, 6, 6), (4, 20, 20), (2, 23, 23), (4, 40, 40), (1, 16, 16), (2, 16, 17), (1, 37, 29)])
 def test_attention_forward_without_stash_any_length(dtype, heads, h, w):
-    """yolo_attn_fwd_nograd (inference / no-grad): <= 448 tokens the one-image kernel without its log-sum-exp store, beyond
-    it the key-blocked online-softmax kernel -- 1600 tokens (preset l @1280: the batched-GEMM route before), exactly one and
-    two key blocks (256, 272), 1073 = a partial last block and a partial last query tile; scores with a spread that makes
-    the running maximum move between blocks; fp32 is not taken (None)."""
-    o = ops()
+    """yolo_attn_fwd_nograd (inference / no-grad): <= 448 tokens (36, 256, 272, 400 here) the one-image kernel without
+    its log-sum-exp store, beyond it the key-blocked online-softmax kernel -- 529, 1073 (a partial last block and a
+    partial last query tile) and 1600 tokens (preset l @1280: the batched-GEMM route before); the first head's scores
+    with a spread that makes the running maximum move between blocks; fp32 is not taken (None).  The key-block boundaries
+    of the long kernel are in test_attention_long_kernel_lengths."""
     n, dk, dh = 2, 32, 64
     qkv = rnd(n, heads * (2 * dk + dh), h, w, seed=53)
     qkv[:, :2 * dk] *= 2.5                            # sharper softmax: per-block maxima differ by several units
-    qkv = nhwc(qkv.to(dtype))
-    scale = dk ** -0.5
-    got = o.attn_fwd_nograd(dev(qkv), heads, dk, dh, scale)
-    if dtype == torch.float32:
-        assert got is None
-        return
-    o_ref, v_ref, _ = emu.attn_fwd(qkv, heads, dk, dh, scale)
-    check(got[0], o_ref, dtype, "attn o (no stash)", mult=2.0)
-    assert torch.equal(got[1].cpu(), v_ref)
-    if h * w <= 448:                                  # the same kernel as the stashing forward: identical output
-        assert torch.equal(got[0], o.attn_fwd(dev(qkv), heads, dk, dh, scale)[0])
+    _nograd_case(dtype, heads, qkv.to(dtype), range(n))
+
+
+# (tokens, images, heads): images * heads * ceil(tokens / 256) below 256 launches 8 waves per workgroup, from 256 on 16
+LONG_CASES = [(449, 3, 3), (512, 3, 4), (513, 3, 3), (768, 3, 4), (1073, 3, 3), (1600, 3, 2),
+              (512, 32, 4), (513, 22, 4), (1600, 19, 2)]
+
+
+@pytest.mark.parametrize("cls", sa.CLASSES)
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("t,n,heads", LONG_CASES)
+def test_attention_long_kernel_lengths(t, n, heads, dtype, cls):
+    """k_attn_fwd_long at its key-block boundaries: 449 (the first length it takes: one full block and 193 keys), 512
+    (exactly two blocks), 513 (one valid key in the last block), 768, 1073, 1600; in the 8-wave launch (3 images) and in
+    the 16-wave launch (batches built from three base images by image_pattern(), every image compared)"""
+    assert (n * heads * ((t + 255) // 256) >= 256) == (n > 3)
+    _nograd_case(dtype, heads, sa.make_qkv(3, heads, 32, 64, t, cls, 100 + t, dtype), sc.image_pattern(n, seed=t), what=f"T={t} {cls} N={n}")
+
+
+def test_attention_nograd_on_a_channel_slice():
+    """the key-blocked kernel and the one-image kernel with ldq = C + 16"""
+    for t in (400, 513):
+        _nograd_case(torch.bfloat16, 3, sa.make_qkv(3, 3, 32, 64, t, "sharp", 110 + t, torch.bfloat16), range(3), pad=16, what=f"T={t} ld = C + 16")
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
