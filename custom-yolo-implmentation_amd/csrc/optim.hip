@@ -5,6 +5,9 @@
 // chunk of one tensor (job found once per workgroup).  Hyper-parameters and the step counter live in device memory so
 // a captured step follows a learning-rate schedule without recapture; GradScaler's scale / found_inf pair is
 // honoured like torch's fused optimizers do (skip the whole step on overflow, unscale the gradient in flight).
+// Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) rides on the same table: k_grad_sqnorm
+// leaves one partial sum of squares per chunk, k_clip_finalize turns them into [total_norm, coef] in device memory and
+// k_adamw multiplies the gradient by coef in flight, next to the unscale (the .grad tensors are not modified).
 #include "common.h"
 
 struct AdamJob {
@@ -52,7 +55,7 @@ __global__ void k_adamw_tick(float* __restrict__ step, const float* __restrict__
 // like torch does on the host (1 - 0.999 in fp32 is off by 5e-5 relative, which shows in exp_avg_sq)
 __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs, int njobs, const double* __restrict__ hyper,
                                                const float* __restrict__ step, const float* __restrict__ grad_scale,
-                                               const float* __restrict__ found_inf) {
+                                               const float* __restrict__ found_inf, const float* __restrict__ clip) {
     if (found_inf != nullptr && *found_inf != 0.f) return;
     __shared__ int sj;
     __shared__ float sc[7];                     // b1, 1-b1, b2, 1-b2, step_size, 1/sqrt(bc2), decay
@@ -72,7 +75,8 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
     const AdamJob j = jobs[sj];
     const float b1 = sc[0], omb1 = sc[1], b2 = sc[2], omb2 = sc[3], step_size = sc[4], bc2s = sc[5], decay = sc[6];
     const float eps = (float)hyper[3];
-    const float gs = grad_scale ? 1.f / *grad_scale : 1.f;      // GradScaler: gradients arrive multiplied by the scale
+    float gs = grad_scale ? 1.f / *grad_scale : 1.f;            // GradScaler: gradients arrive multiplied by the scale
+    if (clip != nullptr) gs *= clip[2];                         // clip state = [max_norm, total_norm, coef]; x * 1.f is x
     const long base = ((long)blockIdx.x - j.cstart) * CHUNK;
     if (j.p_dtype == YOLO_F32 && j.g_dtype == YOLO_F32 && (j.n & 3) == 0 &&
         ((reinterpret_cast<uintptr_t>(j.p) | reinterpret_cast<uintptr_t>(j.g) | reinterpret_cast<uintptr_t>(j.m) |
@@ -97,6 +101,83 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
         j.m[i] = m;
         j.v[i] = v;
         st_any(j.p, j.p_dtype, i, pv);
+    }
+}
+
+// ---- global gradient norm (torch.nn.utils.clip_grad_norm_, norm_type 2; the reference's config.yaml carries
+// training.grad_clip but its loop never reads it).  Same grid as k_adamw: one workgroup per 4096-element chunk writes
+// ONE partial sum of squares with a plain store -- no float atomics, a replay gives the same bits.
+// Accumulation depth: a lane owns 16 elements in four accumulators (4 fused multiply-adds each, the square itself is
+// not rounded), 2 additions join the four, 6 shuffle steps join the wave, 2 additions join the four waves: at most
+// 14 fp32 roundings on any path into a partial, all of non-negative terms, so a partial is within 14 * 2^-24 of its
+// exact value (relative) -- inside the 32 roundings the tests' 2e-6 bound on the norm allows.
+// With found_inf given, the pass also raises it on inf / nan and so replaces k_found_inf on the fp16 route.
+__global__ __launch_bounds__(256) void k_grad_sqnorm(const AdamJob* __restrict__ jobs, int njobs, float* __restrict__ partials,
+                                                     float* __restrict__ found_inf) {
+    __shared__ int sj;
+    __shared__ float sw[4];
+    if (threadIdx.x == 0) {
+        int lo = 0, hi = njobs - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (jobs[mid].cstart <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+        }
+        sj = lo;
+    }
+    __syncthreads();
+    const AdamJob j = jobs[sj];
+    const long base = ((long)blockIdx.x - j.cstart) * CHUNK;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    bool bad = false;
+    if (j.g_dtype == YOLO_F32 && (j.n & 3) == 0 && (reinterpret_cast<uintptr_t>(j.g) & 15) == 0) {
+        for (long i = base + threadIdx.x * 4L; i < base + CHUNK && i < j.n; i += 256 * 4) {
+            const float4 g = *reinterpret_cast<const float4*>((const float*)j.g + i);
+            const float* gp = &g.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc[k] = __fmaf_rn(gp[k], gp[k], acc[k]);
+                bad |= !(fabsf(gp[k]) <= 3.4028234664e38f);     // inf or nan
+            }
+        }
+    } else {
+#pragma unroll
+        for (int it = 0; it < CHUNK / 256; ++it) {
+            const long i = base + threadIdx.x + it * 256L;
+            if (i < j.n) {
+                const float g = ld_any(j.g, j.g_dtype, i);
+                acc[it & 3] = __fmaf_rn(g, g, acc[it & 3]);
+                bad |= !(fabsf(g) <= 3.4028234664e38f);
+            }
+        }
+    }
+    if (found_inf != nullptr && bad) *found_inf = 1.f;        // every writer stores the same value
+    const float w = wave_sum(__fadd_rn(__fadd_rn(acc[0], acc[1]), __fadd_rn(acc[2], acc[3])));
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = __fadd_rn(__fadd_rn(sw[0], sw[1]), __fadd_rn(sw[2], sw[3]));
+}
+
+// One workgroup: the partials summed in a fixed order in double (lane t takes t, t + 256, ...; then a fixed tree), so the
+// result does not depend on scheduling.  state = fp32 [max_norm (read), total_norm, coef (written)];
+// coef = min(1, max_norm / (total_norm + 1e-6)) like clip_grad_norm_ (an infinite norm gives 0, nan gives nan).
+// grad_scale (GradScaler protocol or null): the norm is that of the unscaled gradients.
+__global__ __launch_bounds__(256) void k_clip_finalize(const float* __restrict__ partials, long nparts, float* __restrict__ state,
+                                                       const float* __restrict__ grad_scale) {
+    __shared__ double sd[256];
+    double s = 0.0;
+    for (long i = threadIdx.x; i < nparts; i += 256) s += (double)partials[i];
+    sd[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double inv = grad_scale ? 1.0 / (double)*grad_scale : 1.0;
+        const double norm = sqrt(sd[0]) * inv;
+        const double c = (double)state[0] / (norm + 1e-6);
+        state[1] = (float)norm;
+        state[2] = (float)(c < 1.0 ? c : (c != c ? c : 1.0));
     }
 }
 
@@ -186,7 +267,7 @@ int yolo_adamw_step(const void* jobs_dev, int njobs, long nchunks, const double*
     if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
     hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, found_inf);
     hipLaunchKernelGGL(k_adamw, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step,
-                       grad_scale, found_inf);
+                       grad_scale, found_inf, (const float*)nullptr);
     return YOLO_LAUNCH_CHECK();
 }
 
@@ -199,7 +280,41 @@ int yolo_adamw_amp_step(const void* jobs_dev, int njobs, long nchunks, const dou
     hipLaunchKernelGGL(k_found_inf, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, amp_state + 1);
     hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, amp_state + 1);
     hipLaunchKernelGGL(k_adamw, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step,
-                       amp_state, amp_state + 1);
+                       amp_state, amp_state + 1, (const float*)nullptr);
+    hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, st, amp_state, growth_tracker, growth_factor, backoff_factor, growth_interval);
+    return YOLO_LAUNCH_CHECK();
+}
+
+// ---- clipped step.  Per step: yolo_grad_sqnorm for every job table (each into its own range of ONE partials buffer),
+// one yolo_grad_clip_finalize over the whole buffer, then yolo_adamw_clip_step per table; under device loss scaling the
+// norm pass raises found_inf = amp_state + 1 itself and yolo_amp_update_scale closes the step.
+int yolo_grad_sqnorm(const void* jobs_dev, int njobs, long nchunks, float* partials, float* found_inf, hipStream_t st) {
+    if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
+    if (partials == nullptr) return YOLO_ERR_ARG;
+    hipLaunchKernelGGL(k_grad_sqnorm, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, partials,
+                       found_inf);
+    return YOLO_LAUNCH_CHECK();
+}
+
+int yolo_grad_clip_finalize(const float* partials, long nparts, float* clip_state, const float* grad_scale, hipStream_t st) {
+    if (partials == nullptr || clip_state == nullptr || nparts < 0) return YOLO_ERR_ARG;
+    hipLaunchKernelGGL(k_clip_finalize, dim3(1), dim3(256), 0, st, partials, nparts, clip_state, grad_scale);
+    return YOLO_LAUNCH_CHECK();
+}
+
+int yolo_adamw_clip_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale,
+                         const float* found_inf, const float* clip_state, hipStream_t st) {
+    if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
+    if (clip_state == nullptr) return YOLO_ERR_ARG;
+    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, found_inf);
+    hipLaunchKernelGGL(k_adamw, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step,
+                       grad_scale, found_inf, clip_state);
+    return YOLO_LAUNCH_CHECK();
+}
+
+int yolo_amp_update_scale(float* amp_state, int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval,
+                          hipStream_t st) {
+    if (!(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f) || growth_interval < 1) return YOLO_ERR_ARG;
     hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, st, amp_state, growth_tracker, growth_factor, backoff_factor, growth_interval);
     return YOLO_LAUNCH_CHECK();
 }

@@ -82,8 +82,15 @@ def main(args):
             train_images=data_cfg["train_images"], val_images=data_cfg["val_images"], batch_size=tr_cfg["batch_size"],
             is_test=tr_cfg["is_test"], prefetch_factor=data_cfg.get("prefetch_factor", 2), percent=args.dataset_percent,
             device=args.device, num_classes=model_cfg["num_classes"])
+        # optional key `training.max_grad_norm`: global-norm gradient clipping inside the optimizer step (absent = off).
+        # The reference's `training.grad_clip` is dead there (its loop never reads it) and stays ignored here, so a
+        # reference config keeps reference numerics.
+        max_grad_norm = tr_cfg.get("max_grad_norm", None)
+        if max_grad_norm is not None and args.mode != "ddp":
+            raise ValueError(f"training.max_grad_norm is not supported in {args.mode} mode; use ddp mode or remove the key")
         optimizer, scheduler = get_optimizer(model=model, lr=tr_cfg["learning_rate"], weight_decay=tr_cfg["weight_decay"],
-                                             patience=tr_cfg["learning_rate_patience"], factor=tr_cfg["learning_rate_factor"])
+                                             patience=tr_cfg["learning_rate_patience"], factor=tr_cfg["learning_rate_factor"],
+                                             max_grad_norm=max_grad_norm)
         if args.load_from_checkpoint:
             path = find_latest_checkpoint(ckpt_dir)
             initial_epoch = load_checkpoint(model, optimizer, path, map_location=args.device)
@@ -96,7 +103,7 @@ def main(args):
               log_interval=tr_cfg.get("log_interval", 10), checkpoint_dir=ckpt_dir,
               iou_threshold=tr_cfg.get("iou_threshold", 0.5), conf_threshold=tr_cfg.get("conf_threshold", 0.25),
               distributed_mode=args.mode, precision=args.precision, captured_step=captured,
-              grad_compress=(tr_cfg.get("ddp") or {}).get("grad_compress"))
+              grad_compress=(tr_cfg.get("ddp") or {}).get("grad_compress"), max_grad_norm=max_grad_norm)
     finally:
         if run is not None:
             import wandb

@@ -15,6 +15,12 @@ src/training/train_model.py:247-253).
   parameter's placement, so `torch.distributed.checkpoint` gathers / scatters the optimizer state like torch.optim.AdamW's.
   There GradScaler unscales the gradients itself (`_step_supports_amp_scaling` off: ShardedGradScaler must all-reduce
   found_inf across ranks before anyone steps).
+* `max_grad_norm=c`: `torch.nn.utils.clip_grad_norm_(params, c)` (L2, one norm over ALL parameter groups) folded into the
+  step: one pass over the job tables leaves a partial sum of squares per chunk, one small kernel turns them into
+  `[total_norm, coef]` in device memory, and the AdamW kernel multiplies every gradient by `coef` in flight.  The one
+  deviation from clip_grad_norm_: the `.grad` tensors themselves are NOT modified.  (The reference's config.yaml carries
+  training.grad_clip, but its loop never reads it.)  Not combined with DTensor parameters: the shard norms would need a
+  collective.
 There is no CPU path: parameters must live on the GPU (like every op of this package).
 """
 import torch
@@ -77,18 +83,68 @@ class DeviceGradScaler:
 class HipAdamW(torch.optim.Optimizer):
     _step_supports_amp_scaling = True      # GradScaler hands over grad_scale / found_inf instead of unscaling itself
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=True, max_grad_norm=None):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid AdamW hyper-parameter")
+        # an attribute of the optimizer, NOT a param_groups key and not in state_dict(): checkpoints stay loadable by
+        # torch.optim.AdamW and the reference
+        self.max_grad_norm = max_grad_norm
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                         foreach=None, capturable=True, differentiable=False, fused=True)
         super().__init__(params, defaults)
         if any(isinstance(p, DTensor) for g in self.param_groups for p in g["params"]):
             self._step_supports_amp_scaling = False     # sharded: the scaler unscales and agrees on found_inf across ranks
+            if max_grad_norm is not None:
+                raise ValueError("HipAdamW: max_grad_norm is not supported with DTensor (FSDP2) parameters: the global norm "
+                                 "of sharded gradients needs a collective over the shard norms")
+        self._clip = None                   # dict(state = fp32 [max_norm, total_norm, coef], host = uploaded max_norm, partials)
         self._plans = {}                    # group index -> dict(ptrs, jobs_dev, njobs, nchunks, hyper, hyper_host, step)
         self._pending = []                  # (jobs_dev, pinned host table) awaiting upload after a capture
         # grad_scale / found_inf are NOT pre-defined: GradScaler.step multiplies an existing grad_scale attribute in,
         # sets both around step() and deletes them afterwards
+
+    # ------------------------------------------------------------------------------------------ clipping
+    @property
+    def max_grad_norm(self):
+        """Threshold of the global L2 gradient norm, or None = no clipping.  A new value reaches the device with the next
+        `sync_hyper()` (so a captured step follows it without recapture); switching between None and a number after a
+        capture needs a new capture, because the captured launches differ."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            value = float(value)
+            if not (0.0 < value <= 3.4028234664e38):        # fp32 on the device; also rejects nan
+                raise ValueError(f"HipAdamW: max_grad_norm must be finite and > 0, or None (got {value})")
+        self._max_grad_norm = value
+
+    def _clip_view(self, k):
+        if self._clip is None:
+            raise RuntimeError("HipAdamW: no clipped step has run yet (max_grad_norm is None or step() was not called)")
+        return self._clip["state"][k]
+
+    @property
+    def last_grad_norm(self):
+        """Global L2 norm of the (unscaled) gradients of the last step BEFORE clipping: a 0-dim device view that later
+        steps and replays update in place.  Reading it syncs the host: for logging and tests only."""
+        return self._clip_view(1)
+
+    @property
+    def last_clip_coef(self):
+        """min(1, max_grad_norm / (norm + 1e-6)) of the last step: a 0-dim device view, like `last_grad_norm`."""
+        return self._clip_view(2)
+
+    def _clip_buffers(self, dev, nparts, capturing):
+        c = self._clip
+        if c is None or c["partials"].numel() < nparts or c["state"].device != dev:
+            if capturing:
+                raise RuntimeError("HipAdamW: run one eager step before capturing a graph (the clip buffers are allocated there)")
+            keep = c is not None and c["state"].device == dev      # more chunks than before: the state views stay valid
+            state = c["state"] if keep else torch.tensor([self._max_grad_norm, 0.0, 1.0], dtype=torch.float32, device=dev)
+            c = self._clip = dict(state=state, host=c["host"] if keep else self._max_grad_norm,
+                                  partials=torch.zeros(nparts, dtype=torch.float32, device=dev))
+        return c
 
     # ------------------------------------------------------------------------------------------ state
     def _init_state(self, group, gi):
@@ -126,6 +182,10 @@ class HipAdamW(torch.optim.Optimizer):
             if plan["hyper_host"] != want:
                 plan["hyper"].copy_(torch.tensor(want, dtype=torch.float64))
                 plan["hyper_host"] = want
+        c = self._clip
+        if c is not None and self._max_grad_norm is not None and c["host"] != self._max_grad_norm:
+            c["state"][0:1].copy_(torch.tensor([self._max_grad_norm], dtype=torch.float32))
+            c["host"] = self._max_grad_norm
 
     def finish_capture(self):
         """Upload the job tables recorded while a graph was being captured (call once after the capture ends)."""
@@ -156,6 +216,7 @@ class HipAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        ready = []
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if _grad(p) is not None]
             if not params:
@@ -195,16 +256,53 @@ class HipAdamW(torch.optim.Optimizer):
                 self.sync_hyper()
             elif plan["hyper_host"] is None:
                 raise RuntimeError("HipAdamW: run one eager step (or sync_hyper()) before capturing a graph")
-            amp = getattr(self, "device_amp", None)
-            if amp is not None:     # fp16 loss scaling kept on the device (DeviceGradScaler): found_inf, step, scale update
-                lib.call("yolo_adamw_amp_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
-                         _p(plan["step"]), _p(amp.state), _p(amp.tracker), float(amp.growth_factor), float(amp.backoff_factor),
-                         int(amp.growth_interval), _stream(_loc(params[0])))
+            if self._max_grad_norm is not None:
+                ready.append((plan, params))        # clipped: the norm spans ALL groups, so the launches follow the loop
                 continue
-            lib.call("yolo_adamw_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
-                     _p(plan["step"]), _p(getattr(self, "grad_scale", None)), _p(getattr(self, "found_inf", None)),
-                     _stream(_loc(params[0])))      # GradScaler sets the two attributes around step() and deletes them after
+            self._launch(plan, params)
+        if ready:
+            self._clipped_step(ready)
         return loss
+
+    def _launch(self, plan, params):
+        amp = getattr(self, "device_amp", None)
+        if amp is not None:     # fp16 loss scaling kept on the device (DeviceGradScaler): found_inf, step, scale update
+            lib.call("yolo_adamw_amp_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
+                     _p(plan["step"]), _p(amp.state), _p(amp.tracker), float(amp.growth_factor), float(amp.backoff_factor),
+                     int(amp.growth_interval), _stream(_loc(params[0])))
+            return
+        lib.call("yolo_adamw_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
+                 _p(plan["step"]), _p(getattr(self, "grad_scale", None)), _p(getattr(self, "found_inf", None)),
+                 _stream(_loc(params[0])))      # GradScaler sets the two attributes around step() and deletes them after
+
+    def _clipped_step(self, ready):
+        """Norm pass of every group into ONE partials buffer, one finalize, then the AdamW launches with the clip state.
+        With `device_amp` the norm pass also raises found_inf (it replaces the separate found_inf pass) and the scale
+        update follows the last group; with GradScaler's grad_scale attribute the norm is that of the unscaled gradients."""
+        dev = ready[0][1][0].device
+        st = _stream(ready[0][1][0])
+        capturing = torch.cuda.is_current_stream_capturing()
+        nparts = sum(plan["nchunks"] for plan, _ in ready)
+        clip = self._clip_buffers(dev, nparts, capturing)
+        if not capturing:
+            self.sync_hyper()                       # max_norm, after the buffers exist
+        amp = getattr(self, "device_amp", None)
+        if amp is not None:
+            scale, found, raise_found = amp.state, amp.state[1:2], amp.state[1:2]
+        else:
+            scale, found, raise_found = getattr(self, "grad_scale", None), getattr(self, "found_inf", None), None
+        off = 0
+        for plan, _ in ready:
+            lib.call("yolo_grad_sqnorm", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"],
+                     clip["partials"].data_ptr() + 4 * off, _p(raise_found), st)
+            off += plan["nchunks"]
+        lib.call("yolo_grad_clip_finalize", _p(clip["partials"]), nparts, _p(clip["state"]), _p(scale), st)
+        for plan, _ in ready:
+            lib.call("yolo_adamw_clip_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
+                     _p(plan["step"]), _p(scale), _p(found), _p(clip["state"]), st)
+        if amp is not None:
+            lib.call("yolo_amp_update_scale", _p(amp.state), _p(amp.tracker), float(amp.growth_factor),
+                     float(amp.backoff_factor), int(amp.growth_interval), st)
 
     def _build(self, plan, params, capturing):
         jb = lib.query("yolo_adamw_job_bytes")

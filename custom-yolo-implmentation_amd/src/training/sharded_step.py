@@ -135,6 +135,13 @@ class ShardState:
         return dict(state=state, param_groups=[group])
 
 
+def _refuse_clipping(optimizer):
+    if getattr(optimizer, "max_grad_norm", None) is not None:
+        raise ValueError("ShardedStepRunner: max_grad_norm is not supported on the sharded route -- every rank steps only its "
+                         "shard of the reduce-scattered gradient, so the global norm would need a collective over the shard "
+                         "norms that this runner does not issue; build the optimizer without it")
+
+
 class ShardedStepRunner(TrainStepRunner):
     """See the module docstring.  `optimizer_factory(params) -> optimizer` builds the optimizer over the ONE fp32 shard
     parameter (default: HipAdamW(lr, weight_decay) on the GPU, torch.optim.AdamW elsewhere); or hand in `shard` (a
@@ -142,6 +149,7 @@ class ShardedStepRunner(TrainStepRunner):
 
     def __init__(self, model, criterion, precision="bfloat16", lr=1e-3, weight_decay=1e-2, optimizer_factory=None, use_graph=True,
                  shard=None, optimizer=None):
+        _refuse_clipping(optimizer)
         sh = shard if shard is not None else ShardState(model, precision)
         if (shard is None) != (optimizer is None):
             raise ValueError("ShardedStepRunner: pass `shard` and the `optimizer` built over shard.master together")
@@ -160,6 +168,7 @@ class ShardedStepRunner(TrainStepRunner):
                 else:
                     optimizer_factory = lambda ps: torch.optim.AdamW(ps, lr=lr, weight_decay=weight_decay)
             optimizer = optimizer_factory([self.master])
+            _refuse_clipping(optimizer)
         super().__init__(model, criterion, optimizer, precision="float32", use_graph=use_graph)     # no autocast in FSDP modes
         self.comm, self.staged, self.buckets = False, False, None      # the exchange below replaces the DDP buckets
         # pack: every gradient into its slice of flat_g in one launch (the GradBuckets job table over OUR layout)

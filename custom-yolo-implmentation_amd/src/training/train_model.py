@@ -244,10 +244,21 @@ def _run_epoch(model, loader, criterion, device, autocast_kw, rank, desc, optimi
 def train(model, train_loader, val_loader, optimizer, scheduler, criterion, initial_epoch, num_epochs, device,
           num_classes=171, rank=0, use_wandb=False, wandb_instance=None, log_interval=10,
           checkpoint_dir="experiments/checkpoints", iou_threshold=0.5, conf_threshold=0.25, distributed_mode="ddp",
-          precision="float32", captured_step=None, grad_compress=None):
+          precision="float32", captured_step=None, grad_compress=None, max_grad_norm=None):
     """`captured_step`: None (default) = the captured step where it applies AND has been verified on hardware (ddp mode on
     one GPU, plain parameters, capturable optimizer), True = also with more than one rank, False = the reference's eager
-    loop.  `grad_compress`: None = fp32 gradient exchange (the reference's), "bf16" = bf16 buckets in the captured step."""
+    loop.  `grad_compress`: None = fp32 gradient exchange (the reference's), "bf16" = bf16 buckets in the captured step.
+    `max_grad_norm`: the config's optional training.max_grad_norm, as handed to get_optimizer (the clipping itself lives in
+    HipAdamW.step); here it only refuses the routes that cannot clip and enables the train/grad_norm log."""
+    if max_grad_norm is None:
+        max_grad_norm = getattr(optimizer, "max_grad_norm", None)
+    if max_grad_norm is not None:
+        if distributed_mode in ("fsdp", "fsdp2") or getattr(model, "_native_shard", None) is not None:
+            raise ValueError(f"training.max_grad_norm is not supported in {distributed_mode} mode: the global norm of sharded "
+                             "gradients needs a collective over the shard norms; use ddp mode or remove the key")
+        if getattr(optimizer, "max_grad_norm", None) != float(max_grad_norm):
+            raise ValueError("training.max_grad_norm is set but the optimizer does not clip at it: build the optimizer with "
+                             "get_optimizer(..., max_grad_norm=...)")
     use_amp = precision in ("float16", "bfloat16")
     import torch.distributed as dist
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -276,8 +287,11 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
 
         def log_step(i, ld, epoch=epoch):
             if use_wandb and rank == 0 and wandb_instance is not None and i % log_interval == 0:
-                wandb_instance.log({"train/total_loss": ld["total_loss"], "train/box_loss": ld["box_loss"],
-                                    "train/cls_loss": ld["cls_loss"], "step": epoch * len(train_loader) + i})
+                row = {"train/total_loss": ld["total_loss"], "train/box_loss": ld["box_loss"],
+                       "train/cls_loss": ld["cls_loss"], "step": epoch * len(train_loader) + i}
+                if max_grad_norm is not None:       # pre-clip global norm of this step; read (a host sync) only here
+                    row["train/grad_norm"] = float(optimizer.last_grad_norm)
+                wandb_instance.log(row)
 
         tr = _run_epoch(model, train_loader, criterion, device, autocast_kw, rank,
                         f"[Epoch {epoch + 1}/{num_epochs}] Training", optimizer, scaler, on_step=log_step,

@@ -22,16 +22,22 @@ from src.utils.common import get_num_threads
 _LOWP = ("bfloat16", "float16")
 
 
-def get_optimizer(model: nn.Module, lr: float, weight_decay: float, patience: int, factor: float
-                  ) -> Tuple[optim.Optimizer, optim.lr_scheduler.ReduceLROnPlateau]:
+def get_optimizer(model: nn.Module, lr: float, weight_decay: float, patience: int, factor: float,
+                  max_grad_norm: float = None) -> Tuple[optim.Optimizer, optim.lr_scheduler.ReduceLROnPlateau]:
     """AdamW + ReduceLROnPlateau (reference :20-36).  GPU parameters get the one-launch `HipAdamW` (same update rule,
     state names and scheduler / GradScaler / checkpoint behaviour as torch.optim.AdamW, whose default eager form issues
     several small kernels per parameter): plain parameters (single GPU, DDP) and FSDP2's DTensor parameters, whose local
     shards it updates in place.  FSDP1 (use_orig_params=True) exposes plain-looking nn.Parameters that are views of its
-    flat shards, re-pointed every step: it keeps torch.optim.AdamW, and so does anything on the CPU."""
+    flat shards, re-pointed every step: it keeps torch.optim.AdamW, and so does anything on the CPU.
+    `max_grad_norm` (optional config key training.max_grad_norm; None = off): global-norm gradient clipping inside
+    HipAdamW's step.  Only plain GPU parameters have it: the sharded routes and torch.optim.AdamW raise a ValueError
+    instead of training unclipped."""
     from torch.distributed.tensor import DTensor
     native = getattr(model, "_native_shard", None)
     if native is not None:
+        if max_grad_norm is not None:
+            raise ValueError("training.max_grad_norm is not supported with fsdp2.native_shard: the global norm of sharded "
+                             "gradients needs a collective over the shard norms")
         # `prepare_fsdp2_model(native_shard: true)`: the model is sharded HERE (flat low-precision parameters, this rank's
         # fp32 master shard) and the optimizer steps the master shard; train() drives both through ShardedStepRunner
         from src.training.fused_adamw import HipAdamW
@@ -46,7 +52,10 @@ def get_optimizer(model: nn.Module, lr: float, weight_decay: float, patience: in
     ok = lambda p: (type(p) is nn.Parameter and p.is_cuda) or (isinstance(p, DTensor) and p._local_tensor.is_cuda)
     if params and not fsdp1 and all(ok(p) for p in params):
         from src.training.fused_adamw import HipAdamW
-        opt = HipAdamW(params, lr=lr, weight_decay=weight_decay)
+        opt = HipAdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    elif max_grad_norm is not None:
+        raise ValueError("training.max_grad_norm needs HipAdamW (plain parameters on the GPU: single GPU or ddp mode); "
+                         "FSDP1 and CPU parameters step through torch.optim.AdamW, which does not clip")
     else:
         opt = optim.AdamW(params, lr=lr, weight_decay=weight_decay)
     return opt, optim.lr_scheduler.ReduceLROnPlateau(opt, patience=patience, factor=factor)

@@ -79,6 +79,17 @@ int yolo_adamw_jobs_set_grads(void* jobs_host, int njobs, const void* const* gra
 int yolo_adamw_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale, const float* found_inf, hipStream_t st);
 /* fp16 dynamic loss scaling without the host (GradScaler's scale / step / update, train_model.py:195-208,247-253): amp_state = fp32 [scale, found_inf (0 on entry), last_found_inf]; the gradients carry the factor `scale` (see yolo_loss_dfl_qfl's grad_scale) */
 int yolo_adamw_amp_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, float* amp_state, int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, hipStream_t st);
+/* global-norm gradient clipping on the device (torch.nn.utils.clip_grad_norm_, norm_type 2, then the AdamW step; the reference's
+   config.yaml carries training.grad_clip but its loop, train_model.py:247-253, never reads it): yolo_grad_sqnorm writes one fp32
+   partial sum of squares per chunk of a job table (nchunks floats; found_inf, if not null, is raised on inf / nan);
+   yolo_grad_clip_finalize sums all partials of the step and fills clip_state = fp32 [max_norm (input), total_norm, coef] with
+   coef = min(1, max_norm / (total_norm + 1e-6)), the norm divided by *grad_scale if given; yolo_adamw_clip_step is
+   yolo_adamw_step with every gradient multiplied by coef in flight (the .grad tensors are not modified);
+   yolo_amp_update_scale is the scale update that closes yolo_adamw_amp_step, for a clipped step under device loss scaling */
+int yolo_grad_sqnorm(const void* jobs_dev, int njobs, long nchunks, float* partials, float* found_inf, hipStream_t st);
+int yolo_grad_clip_finalize(const float* partials, long nparts, float* clip_state, const float* grad_scale, hipStream_t st);
+int yolo_adamw_clip_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale, const float* found_inf, const float* clip_state, hipStream_t st);
+int yolo_amp_update_scale(float* amp_state, int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, hipStream_t st);
 /* ---- gradient exchange: pack / unpack every parameter gradient into / out of the flat communication buffers in one launch
    (DistributedDataParallel's bucket copies: src/training/utils_train.py:190); jobs: device copy of a host table of
    yolo_copy_job_bytes() records, dst = src * scale with a dtype cast */
