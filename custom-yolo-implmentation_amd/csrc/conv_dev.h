@@ -2,10 +2,7 @@
 // geometry passed by value, the XCD-aware tile order and the 16-lane row reduction.
 #pragma once
 #include <cstdlib>
-#include "common.h"
-#include "conv_geom.h"
-
-int conv_wide_flag();            // conv_mfma.hip: 16-byte epilogue stores: 2 (default) exchange by v_permlane16_swap, 1 by ds_bpermute, 0 off (YOLO_CONV_WIDE, yolo_conv_wide_set)
+#include "conv_host.h"
 
 namespace {
 
@@ -171,17 +168,13 @@ inline GeomDev to_dev(const ConvGeom& g) {
     d.N = g.N; d.Hs = g.Hs; d.Ws = g.Ws; d.Cs = g.Cs; d.lds = g.lds; d.Hd = g.Hd; d.Wd = g.Wd; d.Cd = g.Cd;
     d.ldd = g.ldd; d.Hg = g.Hg; d.Wg = g.Wg; d.ostep = g.ostep; d.ooff_h = g.ooff_h; d.ooff_w = g.ooff_w;
     d.sstride = g.sstride; d.ntaps = g.ntaps; d.Kpad = g.Kpad; d.KT = g.Kpad / BK;
-    d.dh_pack = d.dw_pack = 0;
+    pack_taps(g, &d.dh_pack, &d.dw_pack);
     d.stats = g.stats;
     d.acc2 = g.acc2; d.ld2 = g.ld2;
     d.act = g.act; d.res = g.res; d.ldr = g.ldr;
     d.wide = conv_wide_flag();
     d.tap_inner = 0;
     d.dma = 1;      // LDS-DMA staging: level or a few % ahead of register staging on every shape of tools/conv_tune.py
-    for (int t = 0; t < g.ntaps; ++t) {
-        d.dh_pack |= (unsigned)(g.dh[t] + 1) << (2 * t);
-        d.dw_pack |= (unsigned)(g.dw[t] + 1) << (2 * t);
-    }
     return d;
 }
 

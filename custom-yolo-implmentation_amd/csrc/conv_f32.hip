@@ -5,8 +5,7 @@
 // of both operands in LDS (k-major, so a thread's four rows / columns are one 16-byte LDS read) and every thread
 // keeps a 4 x 4 register block: 16 FMAs per 8 LDS floats.  Same geometry contract as the other conv kernels
 // (conv_geom.h); summation order differs from the element-wise kernel only in the grouping of the K loop.
-#include "common.h"
-#include "conv_geom.h"
+#include "conv_host.h"
 
 namespace {
 

@@ -1,36 +1,7 @@
 // Dtype-generic (f32 / bf16 / f16, fp32 accumulate) convolution kernels: the correctness anchor and
 // the path for shapes the MFMA kernels do not take (fp32, stem Cin=3, odd channel counts), plus
-// depthwise 3x3, weight packing and the host-side launch logic shared with conv_mfma.hip.
-#include "common.h"
-#include "conv_geom.h"
-
-extern "C" int yolo_bn_stats_acc(const void* y, int ldy, long npix, int C, int dtype, float* acc, hipStream_t st);
-
-// implemented in conv_mfma.hip
-int mfma_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst);
-int mfma_conv_plan(const ConvGeom& g, int dtype);
-int ring_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst);
-int ring_conv_plan(const ConvGeom* gs, int n);
-int up2_conv_variant(const ConvGeom* gs, int dtype);
-int up2_conv_launch(const ConvGeom* gs, int variant, const long* wm_off, long wm_elems, const void* src, const void* wm, void* dst,
-                    int accumulate, int dtype, hipStream_t st);
-int ring_conv_launch(const ConvGeom* gs, int n, const long* wm_off, long wm_elems, const void* src, const void* wm,
-                     const float* bias, void* dst, int accumulate, int dtype, hipStream_t st);
-int mfma_conv_launch(const ConvGeom& g, const void* src, const void* wm, const float* bias, void* dst,
-                     int accumulate, int dtype, hipStream_t st);
-int mfma_wgrad_eligible(int Cin, int Cout, int ldx, int ldy, int dtype, const void* x, const void* dy);
-long mfma_wgrad2_plan(int Kpad, int N, int H, int W, int Cin, int OH, int OW, int Cout, int k);
-long mfma_wgrad2_ws_elems(int Kpad, int N, int H, int W, int Cin, int OH, int OW, int Cout, int k);
-int mfma_wgrad2_launch(const void* x, int ldx, const void* dy, int ldy, float* part, void* dw_oihw, int dw_dtype, int Kpad,
-                       int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, hipStream_t st);
-int f32_conv_eligible(const ConvGeom& g, const void* src, const void* wm, const void* dst);
-int f32_conv_launch(const ConvGeom& g, const float* src, const float* wm, const float* bias, float* dst, int accumulate,
-                    hipStream_t st);
-int f32_wgrad_eligible(const void* x, int ldx, const void* dy, int ldy, int Cin, int Cout);
-int f32_wgrad_launch(const float* x, int ldx, const float* dy, int ldy, float* dwp, int Kpad, int N, int H, int W, int Cin,
-                     int OH, int OW, int Cout, int k, int stride, hipStream_t st);
-int mfma_wgrad_launch(const void* x, int ldx, const void* dy, int ldy, float* dwp, int Kpad, int N, int H, int W,
-                      int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, hipStream_t st);
+// depthwise 3x3, weight packing and the weight-gradient entry point (forward / data-gradient entry points: conv_select.hip).
+#include "conv_host.h"
 
 namespace {
 
@@ -290,9 +261,6 @@ int grid_for(long total) {
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
-extern "C" int yolo_copy_channels(const void* src, int ld_src, void* dst, int ld_dst, long npix, int C, int accumulate, int dtype,
-                                  hipStream_t st);      // elementwise.hip
-
 int launch_generic(const ConvGeom& g, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
                    int dtype, hipStream_t st) {
     long total = (long)g.N * g.Hg * g.Wg * g.Cd;
@@ -317,11 +285,11 @@ int launch_generic(const ConvGeom& g, const void* src, const void* wm, const flo
     return YOLO_LAUNCH_CHECK();
 }
 
-int run_conv(const ConvGeom& g, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
-             int dtype, int algo, hipStream_t st) {
-    if (algo != 1 && mfma_conv_eligible(g, dtype, src, wm, dst))
-        return mfma_conv_launch(g, src, wm, bias, dst, accumulate, dtype, st);
-    if (algo == 2) return YOLO_ERR_ARG;   // MFMA demanded but the shape is not eligible
+}  // namespace
+
+// the VALU / fp32 kernels with what only the MFMA epilogues have (second accumulate source, statistics) as extra passes
+int valu_conv_launch(const ConvGeom& g, const void* src, const void* wm, const float* bias, void* dst, int accumulate, int dtype,
+                     hipStream_t st) {
     int rc = launch_generic(g, src, wm, bias, dst, accumulate, dtype, st);
     if (rc == YOLO_OK && accumulate && g.acc2 != nullptr)      // the generic kernels have one accumulate source: add the second
         rc = yolo_copy_channels(g.acc2, g.ld2, dst, g.ldd, (long)g.N * g.Hd * g.Wd, g.Cd, 1, dtype, st);
@@ -329,46 +297,6 @@ int run_conv(const ConvGeom& g, const void* src, const void* wm, const float* bi
         rc = yolo_bn_stats_acc(dst, g.ldd, (long)g.N * g.Hd * g.Wd, g.Cd, dtype, g.stats, st);
     return rc;
 }
-
-ConvGeom fwd_geom(int ldx, int ldy, float* stats_acc, int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride) {
-    ConvGeom g;
-    g.stats = stats_acc;
-    g.acc2 = nullptr; g.ld2 = 0;
-    g.act = 0; g.res = nullptr; g.ldr = 0;
-    g.N = N; g.Hs = H; g.Ws = W; g.Cs = Cin; g.lds = ldx;
-    g.Hd = OH; g.Wd = OW; g.Cd = Cout; g.ldd = ldy; g.Hg = OH; g.Wg = OW;
-    g.ostep = 1; g.ooff_h = 0; g.ooff_w = 0; g.sstride = stride;
-    int kh[9], kw[9];
-    g.ntaps = conv_taps(0, k, stride, 0, g.dh, g.dw, kh, kw);
-    g.K = g.ntaps * Cin; g.Kpad = round_up32(g.K);
-    return g;
-}
-
-// data gradient, parity class c (stride 2: four classes; stride 1: c = 0)
-ConvGeom dgrad_geom(int lddy, int lddx, int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int c) {
-    ConvGeom g;
-    g.stats = nullptr;
-    g.acc2 = nullptr; g.ld2 = 0;
-    g.act = 0; g.res = nullptr; g.ldr = 0;
-    g.N = N; g.Hs = OH; g.Ws = OW; g.Cs = Cout; g.lds = lddy;
-    g.Hd = H; g.Wd = W; g.Cd = Cin; g.ldd = lddx;
-    int kh[9], kw[9];
-    g.ntaps = conv_taps(1, k, stride, c, g.dh, g.dw, kh, kw);
-    g.K = g.ntaps * Cout; g.Kpad = round_up32(g.K);
-    if (stride == 1) {
-        g.Hg = H; g.Wg = W; g.ostep = 1; g.ooff_h = 0; g.ooff_w = 0; g.sstride = 1;
-    } else {
-        int ph = c >> 1, pw = c & 1;
-        g.Hg = ph == 0 ? (H + 1) / 2 : H / 2;
-        g.Wg = pw == 0 ? (W + 1) / 2 : W / 2;
-        g.ostep = 2; g.ooff_h = ph; g.ooff_w = pw; g.sstride = 1;
-    }
-    return g;
-}
-
-bool supported(int k, int stride) { return (k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)); }
-
-}  // namespace
 
 extern "C" {
 
@@ -391,7 +319,7 @@ long yolo_conv_dgrad_wbuf_elems(int O, int I, int k, int stride) {
 // mode 0: forward matrix [O][Kpad].  mode 1: dgrad buffer (all classes, back to back).
 int yolo_conv_pack_weights(const void* w_oihw, int w_dtype, int O, int I, int k, int stride, int mode, void* out,
                            int out_dtype, hipStream_t st) {
-    if (!supported(k, stride)) return YOLO_ERR_ARG;
+    if (!conv_supported(k, stride)) return YOLO_ERR_ARG;
     int ncls = (mode == 1 && stride == 2) ? 4 : 1;
     long off = 0;
     for (int c = 0; c < ncls; ++c) {
@@ -427,109 +355,8 @@ int yolo_conv_unpack_wgrad(const float* dwp, int O, int I, int k, void* dw_oihw,
     return YOLO_LAUNCH_CHECK();
 }
 
-// y[N,OH,OW,Cout] = conv(x[N,H,W,Cin], w) (+ bias); pad = k/2; wp = forward-packed weights in `dtype`.
-// algo: 0 auto (MFMA when eligible), 1 generic VALU kernel, 2 MFMA or error.
-// stats_acc (optional, needs bias == null): fp32 [8][2][Cout], pre-zeroed; receives sum(y) and sum(y^2) per channel
-// (of the values as stored) for the BatchNorm that follows -- from the MFMA kernel's epilogue, no extra pass.
-int yolo_conv2d_fwd(const void* x, int ldx, const void* wp, const float* bias, void* y, int ldy, float* stats_acc, int N,
-                    int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, int algo,
-                    hipStream_t st) {
-    if (!supported(k, stride) || (stats_acc && bias)) return YOLO_ERR_ARG;
-    int pad = k / 2;
-    if (OH != (H + 2 * pad - k) / stride + 1 || OW != (W + 2 * pad - k) / stride + 1) return YOLO_ERR_ARG;
-    ConvGeom g = fwd_geom(ldx, ldy, stats_acc, N, H, W, Cin, OH, OW, Cout, k, stride);
-    return run_conv(g, x, wp, bias, y, 0, dtype, algo, st);
-}
-
-// Inference form of a fused Conv block (Model.fuse(): BatchNorm folded into the weights and a bias, reference
-// src/model/model_blocks.py:36-37, src/utils/model_utils.py:72-118): y = act(conv(x) + bias) (+ res) in ONE launch -- bias,
-// SiLU and the residual add of Residual / PSABlock ride in the epilogue of the MFMA kernels.  Returns 1 (nothing launched)
-// when the shape / dtype has no MFMA kernel (fp32, unaligned channels): the caller then runs conv + the element-wise pass.
-int yolo_conv2d_fwd_act(const void* x, int ldx, const void* wp, const float* bias, const void* res, int ldr, void* y, int ldy,
-                        int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int act, int dtype,
-                        hipStream_t st) {
-    if (!supported(k, stride) || (act != 0 && act != 1)) return YOLO_ERR_ARG;
-    int pad = k / 2;
-    if (OH != (H + 2 * pad - k) / stride + 1 || OW != (W + 2 * pad - k) / stride + 1) return YOLO_ERR_ARG;
-    if (res != nullptr && ((ldr & 3) || (reinterpret_cast<uintptr_t>(res) & 7))) return 1;
-    ConvGeom g = fwd_geom(ldx, ldy, nullptr, N, H, W, Cin, OH, OW, Cout, k, stride);
-    g.act = act; g.res = res; g.ldr = ldr;
-    if (!mfma_conv_eligible(g, dtype, x, wp, y)) return 1;
-    return mfma_conv_launch(g, x, wp, bias, y, 0, dtype, st);
-}
-
-// dx[N,H,W,Cin] (= or +=) conv^T(dy[N,OH,OW,Cout]); wb = dgrad-packed buffer from yolo_conv_pack_weights(mode 1)
-static int conv2d_dgrad_impl(const void* dy, int lddy, const void* wb, void* dx, int lddx, const void* acc2, int ld2, int N, int H,
-                            int W, int Cin, int OH, int OW, int Cout, int k, int stride, int accumulate, int dtype, int algo,
-                            hipStream_t st);
-
-int yolo_conv2d_dgrad(const void* dy, int lddy, const void* wb, void* dx, int lddx, int N, int H, int W, int Cin,
-                      int OH, int OW, int Cout, int k, int stride, int accumulate, int dtype, int algo,
-                      hipStream_t st) {
-    return conv2d_dgrad_impl(dy, lddy, wb, dx, lddx, nullptr, 0, N, H, W, Cin, OH, OW, Cout, k, stride, accumulate, dtype, algo, st);
-}
-
-// dx = dgrad + dx + acc2: the data gradient accumulated into dx together with a SECOND tensor of dx's shape (row stride ld2)
-// in the same epilogue -- a three-way gradient fan-in (C3K2: the chunk's half feeds the concat and a Residual whose own
-// skip gradient is a third term) without an extra pass.  Stride 1 only.
-int yolo_conv2d_dgrad_acc2(const void* dy, int lddy, const void* wb, void* dx, int lddx, const void* acc2, int ld2, int N, int H,
-                           int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, int algo, hipStream_t st) {
-    if (stride != 1 || acc2 == nullptr || (ld2 & 3) || (reinterpret_cast<uintptr_t>(acc2) & 7)) return YOLO_ERR_ARG;
-    return conv2d_dgrad_impl(dy, lddy, wb, dx, lddx, acc2, ld2, N, H, W, Cin, OH, OW, Cout, k, stride, 1, dtype, algo, st);
-}
-
-static int conv2d_dgrad_impl(const void* dy, int lddy, const void* wb, void* dx, int lddx, const void* acc2, int ld2, int N, int H,
-                            int W, int Cin, int OH, int OW, int Cout, int k, int stride, int accumulate, int dtype, int algo,
-                            hipStream_t st) {
-    if (!supported(k, stride)) return YOLO_ERR_ARG;
-    size_t esz = dtype == YOLO_F32 ? 4 : 2;
-    int ncls = stride == 2 ? 4 : 1;
-    ConvGeom gs[4];
-    long offs[4], off = 0;
-    bool ring = algo != 1 && stride == 2;
-    for (int c = 0; c < ncls; ++c) {
-        gs[c] = dgrad_geom(lddy, lddx, N, H, W, Cin, OH, OW, Cout, k, stride, c);
-        gs[c].acc2 = acc2; gs[c].ld2 = ld2;
-        offs[c] = off;
-        ring = ring && ring_conv_eligible(gs[c], dtype, dy, wb, dx);
-        off += (long)Cin * gs[c].Kpad;
-    }
-    if (algo != 1 && stride == 2)                             // large maps: the dy patch once for all four classes (conv_up2.hip)
-        if (const int uv = up2_conv_variant(gs, dtype)) return up2_conv_launch(gs, uv, offs, off, dy, wb, dx, accumulate, dtype, st);
-    if (ring)                                                 // one launch for the four parity classes
-        return ring_conv_launch(gs, 4, offs, off, dy, wb, nullptr, dx, accumulate, dtype, st);
-    for (int c = 0; c < ncls; ++c) {
-        const ConvGeom& g = gs[c];
-        if (g.Hg > 0 && g.Wg > 0) {
-            int rc = run_conv(g, dy, (const char*)wb + offs[c] * esz, nullptr, dx, accumulate, dtype, algo, st);
-            if (rc) return rc;
-        }
-    }
-    return YOLO_OK;
-}
-
-// Which kernel a forward / data-gradient launch takes (tests assert that their shapes reach the variant they mean to cover).
-int yolo_conv2d_plan(int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int mode, int cls, int dtype) {
-    if (!supported(k, stride)) return -1;
-    const ConvGeom g = mode == 0 ? fwd_geom(Cin, Cout, nullptr, N, H, W, Cin, OH, OW, Cout, k, stride)
-                                 : dgrad_geom(Cout, Cin, N, H, W, Cin, OH, OW, Cout, k, stride, cls);
-    static const long long dummy[2] = {0, 0};               // eligibility looks at alignment only
-    if (!mfma_conv_eligible(g, dtype, dummy, dummy, dummy)) return 0;
-    if (mode == 1 && stride == 2) {                           // the four parity classes go out as one ring launch when all qualify
-        ConvGeom gs[4];
-        bool all = true;
-        for (int c = 0; c < 4; ++c) {
-            gs[c] = dgrad_geom(Cout, Cin, N, H, W, Cin, OH, OW, Cout, k, stride, c);
-            all = all && ring_conv_eligible(gs[c], dtype, dummy, dummy, dummy);
-        }
-        if (const int uv = up2_conv_variant(gs, dtype)) return 5000 + uv;
-        if (all) return ring_conv_plan(gs, 4);
-    }
-    return mfma_conv_plan(g, dtype);
-}
-
 long yolo_conv2d_wgrad_plan(int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype) {
-    if (!supported(k, stride)) return -1;
+    if (!conv_supported(k, stride)) return -1;
     static const long long dummy[2] = {0, 0};
     if (!mfma_wgrad_eligible(Cin, Cout, Cin, Cout, dtype, dummy, dummy)) return 0;
     return mfma_wgrad2_plan(round_up32(k * k * Cin), N, H, W, Cin, OH, OW, Cout, k);
@@ -549,7 +376,7 @@ static int wgrad_path(const void* x, int ldx, const void* dy, int ldy, int N, in
 // fp32 scratch elements yolo_conv2d_wgrad needs for these arguments
 long yolo_conv2d_wgrad_ws_elems(const void* x, int ldx, const void* dy, int ldy, int N, int H, int W, int Cin, int OH,
                                 int OW, int Cout, int k, int stride, int dtype, int algo) {
-    if (!supported(k, stride)) return 0;
+    if (!conv_supported(k, stride)) return 0;
     const int Kpad = round_up32(k * k * Cin);
     if (wgrad_path(x, ldx, dy, ldy, N, H, W, Cin, OH, OW, Cout, dtype, algo) == 2)
         return mfma_wgrad2_ws_elems(Kpad, N, H, W, Cin, OH, OW, Cout, k);
@@ -561,7 +388,7 @@ long yolo_conv2d_wgrad_ws_elems(const void* x, int ldx, const void* dy, int ldy,
 int yolo_conv2d_wgrad(const void* x, int ldx, const void* dy, int ldy, float* ws, void* dw_oihw, int dw_dtype, int N,
                       int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, int algo,
                       hipStream_t st) {
-    if (!supported(k, stride)) return YOLO_ERR_ARG;
+    if (!conv_supported(k, stride)) return YOLO_ERR_ARG;
     const int K = k * k * Cin, Kpad = round_up32(K);
     const int path = wgrad_path(x, ldx, dy, ldy, N, H, W, Cin, OH, OW, Cout, dtype, algo);
     if (path == 2)
@@ -602,12 +429,6 @@ static dim3 dw_grid(int nrows, int cv) {
     int tpr = cv < 256 ? cv : 256;
     return dim3((unsigned)(nrows < 4096 ? nrows : 4096), (unsigned)ceil_div(cv, tpr));
 }
-
-// dwconv.hip: the strip kernels for 16-bit tensors with 8-channel alignment (-1 = does not qualify)
-int dw_strip_launch(bool flip, const void* x, int ldx, const float* w, void* y, int ldy, int N, int H, int W, int C, int dtype,
-                    int accumulate, float* stats, hipStream_t st, const float* bias = nullptr, int act = 0);
-int dw_strip_wgrad_launch(const void* x, int ldx, const void* dy, int ldy, float* partial, int nslab, int N, int H, int W, int C,
-                          int dtype, hipStream_t st);
 
 template <bool FLIP>
 static int dw_launch(const void* x, int ldx, const float* w, void* y, int ldy, int N, int H, int W, int C, int dtype,

@@ -65,5 +65,14 @@ static inline int conv_taps(int mode, int k, int stride, int cls, int* dh, int* 
 // Kernel-selection overrides (tile widths, K order, halo variant, LDS-DMA, ring kernel on/off, ring depth); 0 / -1 =
 // automatic.  Read ONCE per process from YOLO_CONV_TUNE ("bn,tap_inner,halo,dma,ring,bm,nst,bk"); tools/conv_tune.py and the
 // variant-forcing parity tests change them through yolo_conv_tune_set.  Nothing on the training path writes them.
+// The third field steers three kernel families: conv_force (conv_select.hip) decodes it and holds the value table.
 struct ConvTune { int bn, tap_inner, halo, dma, ring, bm, nst, bk; };
-ConvTune& conv_tune();
+
+// tap offsets as the MFMA kernels take them: 2 bits per tap, value + 1
+static inline void pack_taps(const ConvGeom& g, unsigned* dh_pack, unsigned* dw_pack) {
+    *dh_pack = *dw_pack = 0;
+    for (int t = 0; t < g.ntaps; ++t) {
+        *dh_pack |= (unsigned)(g.dh[t] + 1) << (2 * t);
+        *dw_pack |= (unsigned)(g.dw[t] + 1) << (2 * t);
+    }
+}

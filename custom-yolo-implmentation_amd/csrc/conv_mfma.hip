@@ -3,9 +3,10 @@
 // Forward and data-gradient share one kernel (ConvGeom, conv_geom.h): a 128-pixel x BN-channel
 // output tile per 256-thread workgroup (4 waves), K = taps*Cs walked in 32-element steps.  The
 // activation tile is gathered NHWC row by row (16 B = 8 channels per lane, zero for padding taps),
-// the weight tile comes from the K-major packed matrix; both are staged through LDS (80-byte
-// rows: 64 B payload + 16 B pad to spread ds_read_b128 over the banks) with a register-staged
-// double buffer, one barrier per K-step.  MFMA roles are swapped (A = weights, B = activations) so a
+// the weight tile comes from the K-major packed matrix; both are staged through LDS (unpadded
+// 64-byte rows whose four 16-byte chunks are XOR-swizzled by the row, LDSROW in conv_dev.h: conflict-free
+// ds_read_b128 fragment reads) with a double buffer filled by LDS-DMA or through registers, one
+// barrier per K-step.  MFMA roles are swapped (A = weights, B = activations) so a
 // lane's four accumulator registers are four CONSECUTIVE output channels of one pixel: the epilogue
 // stores 8 bytes per lane into NHWC rows.
 //
@@ -13,33 +14,7 @@
 // pixel, which is the slow axis of NHWC, so both tiles are transposed on their way into LDS
 // (pixel-major inner) and the K loop runs over 32-pixel steps of one slab; slabs are combined with
 // fp32 atomics into the packed gradient matrix.
-#include <cstdio>
-#include <cstdlib>
-#include "common.h"
-#include "conv_geom.h"
 #include "conv_dev.h"
-
-int halo_conv_eligible(const ConvGeom& g);
-int rows_conv_eligible(const ConvGeom& g);
-int rows_conv_launch(const ConvGeom& g, int variant, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
-                     int dtype, hipStream_t st);
-int halo_conv_launch(const ConvGeom& g, int variant, const void* src, const void* wm, const float* bias, void* dst,
-                     int accumulate, int dtype, hipStream_t st);
-
-ConvTune& conv_tune() {
-    static ConvTune t = [] {
-        ConvTune v{0, -1, -1, -1, -1, 0, 0, 0};
-        if (const char* e = getenv("YOLO_CONV_TUNE"))
-            sscanf(e, "%d,%d,%d,%d,%d,%d,%d,%d", &v.bn, &v.tap_inner, &v.halo, &v.dma, &v.ring, &v.bm, &v.nst, &v.bk);
-        return v;
-    }();
-    return t;
-}
-
-int ring_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst);
-int ring_conv_plan(const ConvGeom* gs, int n);
-int ring_conv_launch(const ConvGeom* gs, int n, const long* wm_off, long wm_elems, const void* src, const void* wm,
-                     const float* bias, void* dst, int accumulate, int dtype, hipStream_t st);
 
 namespace {
 
@@ -447,26 +422,9 @@ void launch_tile(const GeomDev& d, const void* src, const void* wm, const float*
 #undef CONV_LAUNCH
 }
 
-// Tile width (tools/conv_tune.py on MI355X): the widest channel tile that still yields one workgroup per CU --
-// small maps with many channels (20x20, K in the thousands) otherwise run ~100 workgroups through a 144-step
-// K loop on a 256-CU chip; narrower tiles than that only add LDS reads per MFMA.  One-tap convs whose source
-// stays in the 256 MB Infinity Cache prefer 64-wide tiles (re-reading the source per channel tile is cheap there).
-int conv_tile_bn(const GeomDev& d_in) {
-    const long tm = ((long)d_in.N * d_in.Hg * d_in.Wg + BM - 1) / BM;
-    auto blocks = [&](int bn) { return tm * ((d_in.Cd + bn - 1) / bn); };
-    int bn = d_in.Cd > 64 ? 128 : (d_in.Cd > 32 ? 64 : 32);
-    const long src_bytes = (long)d_in.N * d_in.Hs * d_in.Ws * d_in.lds * 2;
-    if (bn == 128 && d_in.ntaps == 1 && src_bytes <= (128L << 20)) bn = 64;
-    while (bn > 32 && blocks(bn) < 256) bn >>= 1;
-    const ConvTune& tu = conv_tune();                        // overrides: tuning runs and variant-forcing tests only
-    if (tu.bn == 32 || tu.bn == 64 || tu.bn == 128) bn = tu.bn;
-    return bn;
-}
-
 template <typename T>
-void launch_conv_t(const GeomDev& d_in, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
+void launch_conv_t(const GeomDev& d_in, int bn, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
                    hipStream_t st) {
-    const int bn = conv_tile_bn(d_in);
     GeomDev d = d_in;
     const ConvTune& tu = conv_tune();
     if (tu.tap_inner >= 0) d.tap_inner = tu.tap_inner;
@@ -480,12 +438,6 @@ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
-extern "C" int yolo_conv_tune_set(int bn, int tap_inner, int halo, int dma, int ring, int bm, int nst, int bk) {
-    ConvTune& t = conv_tune();
-    t.bn = bn; t.tap_inner = tap_inner; t.halo = halo; t.dma = dma; t.ring = ring; t.bm = bm; t.nst = nst; t.bk = bk;
-    return YOLO_OK;
-}
-
 static int& wide_state() {
     static int v = [] { const char* e = getenv("YOLO_CONV_WIDE"); const int m = e ? atoi(e) : 2; return m < 0 ? 0 : m > 2 ? 2 : m; }();
     return v;
@@ -495,82 +447,30 @@ int conv_wide_flag() { return wide_state(); }
 // through v_permlane16_swap
 extern "C" int yolo_conv_wide_set(int on) { wide_state() = on < 0 ? 0 : on > 2 ? 2 : on; return YOLO_OK; }
 
-int mfma_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst) {
+// What the MFMA families (this file, conv_halo / conv_ring / conv_rows.hip) share: addressing and alignment
+int mfma_conv_addressable(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst) {
     if (dtype != YOLO_BF16 && dtype != YOLO_F16) return 0;
-    if (g.Cs % 8 || g.lds % 8 || g.Cd % 8 || g.ldd % 4) return 0;
+    if (g.lds % 8 || g.Cd % 8 || g.ldd % 4) return 0;
     // 32-bit byte offsets / buffer descriptors in the gather, 32-bit pixel indices
     if ((long)g.N * g.Hs * g.Ws * g.lds + (long)(g.Ws + 1) * g.lds >= (1L << 30)) return 0;
-    if ((long)g.N * g.Hg * g.Wg + 256 >= (1L << 31) || (long)g.Cd * g.Kpad >= (1L << 30)) return 0;
+    if ((long)g.N * g.Hg * g.Wg + 256 >= (1L << 31)) return 0;
     if (!al16(src) || !al16(wm) || (reinterpret_cast<uintptr_t>(dst) & 7)) return 0;
     for (int t = 0; t < g.ntaps; ++t)
         if (g.dh[t] < -1 || g.dh[t] > 1 || g.dw[t] < -1 || g.dw[t] > 1) return 0;
     return 1;
 }
 
-// 3x3 stride-1 layers take the halo kernel (conv_halo.hip) when the map is large enough for its 8x16 / 16x16 pixel
-// tiles to fill the chip; variant choice from tools/conv_tune.py.  yolo_conv_tune_set's third field overrides it
-// (0 = gather kernel, 1..4 = halo variant) for tuning runs and the variant-forcing parity tests.
-static int halo_variant(const ConvGeom& g) {
-    const int v = conv_tune().halo;
-    if (!halo_conv_eligible(g)) return 0;
-    if (v >= 0 && v <= 4) return v;                          // 5..7 steer the row-block kernel only
-    // measured in the training step (preset s, 32 images): the halo kernel wins on maps of 80x80 and more
-    // (16x16-pixel tiles: 63 vs 81 us for 128->64 @80x80) and on 40x40 with exactly two 64-channel wave columns;
-    // on smaller maps / other widths its tiles are too few or half empty and the gather kernel is level or better
-    if ((long)g.Hg * g.Wg >= 80 * 80) return g.Cd >= 128 ? 2 : 3;
-    if (g.Hg >= 40 && g.Wg >= 40 && g.Cd == 128) return 1;
-    return 0;
+// Shapes with an MFMA kernel at all (the gather kernel takes every one of them; which family runs: conv_select.hip)
+int mfma_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst) {
+    return mfma_conv_addressable(g, dtype, src, wm, dst) && g.Cs % 8 == 0 && (long)g.Cd * g.Kpad < (1L << 30);
 }
 
-// Maps 20 or 40 pixels wide: the row-block kernel (conv_rows.hip).  Returns 0 (not taken) or its variant (1 / 3 = 80 pixels
-// x 64 channels per workgroup with four / three weight stages, 2 = 80 x 128, 4 = 160 x 64).  yolo_conv_tune_set's third
-// field: 5 = default choice wherever eligible, 6 / 7 / 8 / 12 = force variant 1 / 2 / 3 / 4, 14 = variant 6 (10 rows of a
-// 16-pixel-wide block x 64 channels, maps of any width), 0..4 and 9 = never.
-// Default (tools/rows_bench.py, graph-replayed, 32 images, against the gather ring): 40-wide maps take the 160 x 64 tile
-// (256->256: 83 -> 63 us, 64->64: 15.0 -> 12.8, 256->64: 38 -> 25), 20-wide maps too once the 80 x 64 tiling would put two
-// workgroups on every CU (256->256: 35 -> 24 us), otherwise 80 x 64 (128->128: 17.8 -> 11.7, 512->64: 42.6 -> 21.5).
-static int rows_variant(const ConvGeom& g) {
-    const int v = conv_tune().halo;
-    const int el = rows_conv_eligible(g);
-    if (!el) return 0;
-    if ((v >= 0 && v < 5) || v == 9) return 0;               // 9: this kernel off, everything else automatic (A/B runs)
-    // narrow layers (fewer than 64 destination channels): 20 x 16 pixels x 32 channels.  Ahead of the gather kernels with a full
-    // 32-channel source chunk (64->32 @80x80 forward 28.4 -> 21.0 us, its 32->64 data gradient 26.1 -> 18.6; 32->16 @160x160
-    // forward 41.9 -> 36.5), behind them with a 16-channel source (half-empty chunks): 16 = forced, tests
-    if (el == 3) return (v == 16 || ((v < 0 || v == 5) && g.Cs % 32 == 0)) ? 7 : 0;
-    if (v == 14) return 6;                                   // 16-pixel-wide blocks, any map width
-    // wider maps: 10 x 16-pixel blocks x 64 channels beat the halo kernel where the layer has exactly one 64-channel tile
-    // (64->64 @80x80 35 -> 31 us forward, 31.5 -> 26.8 data gradient; 128->64 forward 51.5 -> 41.5; 64->64 @160x160 104 -> 97)
-    if (el != 1) return (v < 0 || v == 5) && g.Cd == 64 && g.Cs >= 64 ? 6 : 0;          // 15: full-row blocks only (A/B)
-    if (v == 6) return 1;
-    if (v == 7) return g.Cd > 64 ? 2 : 1;
-    if (v == 8) return 3;
-    if (v == 12) return 4;
-    if (g.Wg == 40) return 4;
-    const long wgs = (long)g.N * ((g.Hg + 3) / 4) * ((g.Cd + 63) / 64);
-    return wgs >= 512 ? 4 : 3;
-}
-
-int mfma_conv_plan(const ConvGeom& g, int dtype) {
-    static const long long dummy[2] = {0, 0};
-    if (const int rv = rows_variant(g)) return 4000 + rv;
-    if (const int hv = halo_variant(g)) return 2000 + hv;
-    if (ring_conv_eligible(g, dtype, dummy, dummy, dummy)) return ring_conv_plan(&g, 1);
-    return 1000 + conv_tile_bn(to_dev(g));
-}
-
-int mfma_conv_launch(const ConvGeom& g, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
+// the gather kernel with a bn-channel tile (32 / 64 / 128)
+int mfma_conv_launch(const ConvGeom& g, int bn, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
                      int dtype, hipStream_t st) {
-    if ((long)g.N * g.Hg * g.Wg == 0) return YOLO_OK;
-    if (const int rv = rows_variant(g)) return rows_conv_launch(g, rv, src, wm, bias, dst, accumulate, dtype, st);
-    if (const int hv = halo_variant(g)) return halo_conv_launch(g, hv, src, wm, bias, dst, accumulate, dtype, st);
-    if (ring_conv_eligible(g, dtype, src, wm, dst)) {
-        const long off0 = 0;
-        return ring_conv_launch(&g, 1, &off0, (long)g.Cd * g.Kpad, src, wm, bias, dst, accumulate, dtype, st);
-    }
     GeomDev d = to_dev(g);
-    if (dtype == YOLO_BF16) launch_conv_t<bf16_t>(d, src, wm, bias, dst, accumulate, st);
-    else launch_conv_t<f16_t>(d, src, wm, bias, dst, accumulate, st);
+    if (dtype == YOLO_BF16) launch_conv_t<bf16_t>(d, bn, src, wm, bias, dst, accumulate, st);
+    else launch_conv_t<f16_t>(d, bn, src, wm, bias, dst, accumulate, st);
     return YOLO_LAUNCH_CHECK();
 }
 

@@ -20,8 +20,6 @@
 // (A = weights, B = activations): a lane's four accumulator registers are four consecutive output channels.
 #include "conv_dev.h"
 
-int halo_conv_eligible(const ConvGeom& g);
-
 namespace {
 
 struct RingSub {
@@ -277,8 +275,6 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
     }
 }
 
-struct RingTile { int bm, bn, nst, bk; };
-
 template <typename T, int RB, int WGM, int WGN, int WM, int WN, int NST>
 void launch_ring_t(const RingGeom& g, int nwg, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
                    hipStream_t st) {
@@ -318,71 +314,19 @@ int launch_ring(const RingGeom& g, const RingTile& t, int nwg, const void* src, 
 
 }  // namespace
 
-// Shapes the ring kernel takes: `ring` = 1 (yolo_conv_tune_set) forces it wherever it can run, 0 turns it off, -1 (the
-// default) uses it where tools/ring_tune.py measured it ahead of the gather kernel on MI355X: maps of 40x40 and below
-// with K >= 256 (every step a full cache line per row, half the barriers, the load of step t+1 under the MFMAs of step
-// t), and 80x80 maps with K >= 1024.  Larger maps are HBM-bound streams that want the gather kernel's occupancy
-// (12 KB of LDS per workgroup instead of 48+).
+// Shapes the ring kernel can run (where it is USED: conv_select.hip): what the MFMA families share, source channels a
+// multiple of 32 and at least 64, and a weight matrix the kernel's byte offsets reach with room for its four sub-problems.
 int ring_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst) {
-    const int mode = conv_tune().ring;
-    if (mode == 0) return 0;
-    if (mode < 0) {
-        const long pix = (long)g.N * g.Hd * g.Wd / (g.ostep * g.ostep);       // pixels of one launch (a parity class: a quarter)
-        const int steps = g.ntaps * ((g.Cs + 63) / 64);
-        const long all_pix = (long)g.N * g.Hd * g.Wd;
-        if (!((all_pix <= 60000 && (steps >= 4 || g.ostep == 2)) || (all_pix <= 240000 && steps >= 16))) return 0;
-        (void)pix;
-    }
-    if (dtype != YOLO_BF16 && dtype != YOLO_F16) return 0;
-    if (g.Cs % 32 || g.Cs < 64 || g.lds % 8 || g.Cd % 8 || g.ldd % 4) return 0;
-    if ((long)g.N * g.Hs * g.Ws * g.lds + (long)(g.Ws + 1) * g.lds >= (1L << 30)) return 0;
-    if ((long)g.N * g.Hg * g.Wg + 256 >= (1L << 31) || (long)g.Cd * g.Kpad * 4 >= (1L << 30)) return 0;
-    if ((reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(wm) & 15) || (reinterpret_cast<uintptr_t>(dst) & 7)) return 0;
-    for (int t = 0; t < g.ntaps; ++t)
-        if (g.dh[t] < -1 || g.dh[t] > 1 || g.dw[t] < -1 || g.dw[t] > 1) return 0;
-    return 1;
-}
-
-// Tile choice.  Pixel tiles of 128 while that still gives every CU a workgroup, else 64; channel tiles of 128 for wide
-// layers while the grid stays at a workgroup per CU, else 64 (32 for <= 32 channels).  K-step and ring depth from
-// tools/conv_tune.py (see the table in DESIGN.md).
-static RingTile ring_tile(long pix_tiles128, long pix_tiles64, int Cd, int Cs) {
-    RingTile t;
-    auto wgs = [&](int bm, int bn) { return (bm == 128 ? pix_tiles128 : pix_tiles64) * ((Cd + bn - 1) / bn); };
-    t.bn = Cd > 64 ? 128 : (Cd > 32 ? 64 : 32);
-    t.bm = 128;
-    if (t.bn == 128 && wgs(128, 128) < 256) t.bn = 64;
-    if (t.bn != 32 && wgs(128, t.bn) < 256) t.bm = 64;
-    const ConvTune& tu = conv_tune();
-    if (tu.bn == 32 || tu.bn == 64 || tu.bn == 128) t.bn = tu.bn;
-    if (tu.bm == 64 || tu.bm == 128) t.bm = tu.bm;
-    t.bk = 64;
-    if (tu.bk == 32 || tu.bk == 64) t.bk = tu.bk;
-    if (t.bn == 32) { t.bm = 128; t.bk = 64; }                // the 32-channel tile exists for 64-deep steps only
-    t.nst = 2;
-    if (tu.nst >= 2 && tu.nst <= 4) t.nst = tu.nst;
-    return t;
-}
-
-static long pix_tiles(const ConvGeom* gs, int n, int bm) {
-    long s = 0;
-    for (int c = 0; c < n; ++c) s += ((long)gs[c].N * gs[c].Hg * gs[c].Wg + bm - 1) / bm;
-    return s;
-}
-
-int ring_conv_plan(const ConvGeom* gs, int n) {
-    const RingTile t = ring_tile(pix_tiles(gs, n, 128), pix_tiles(gs, n, 64), gs[0].Cd, gs[0].Cs);
-    return 3000 + (t.bm == 64 ? 500 : 0) + t.bn;
+    return mfma_conv_addressable(g, dtype, src, wm, dst) && g.Cs % 32 == 0 && g.Cs >= 64 && (long)g.Cd * g.Kpad * 4 < (1L << 30);
 }
 
 // gs[0..n): sub-problems that share source, destination tensor, channel counts and strides (n = 1, or the four parity
 // classes of a stride-2 data gradient; empty classes are skipped); wm_off[c] = element offset of class c's packed
 // weight matrix inside wm, wm_elems = size of the whole buffer
-int ring_conv_launch(const ConvGeom* gs, int n, const long* wm_off, long wm_elems, const void* src, const void* wm,
-                     const float* bias, void* dst, int accumulate, int dtype, hipStream_t st) {
+int ring_conv_launch(const ConvGeom* gs, int n, const RingTile& t, const long* wm_off, long wm_elems, const void* src,
+                     const void* wm, const float* bias, void* dst, int accumulate, int dtype, hipStream_t st) {
     if (n < 1 || n > 4 || wm_elems >= (1L << 30)) return YOLO_ERR_ARG;
     const ConvGeom& g0 = gs[0];
-    const RingTile t = ring_tile(pix_tiles(gs, n, 128), pix_tiles(gs, n, 64), g0.Cd, g0.Cs);
     RingGeom d;
     d.N = g0.N; d.Hs = g0.Hs; d.Ws = g0.Ws; d.Cs = g0.Cs; d.lds = g0.lds; d.Hd = g0.Hd; d.Wd = g0.Wd; d.Cd = g0.Cd; d.ldd = g0.ldd;
     d.ostep = g0.ostep; d.sstride = g0.sstride; d.stats = g0.stats;
@@ -401,11 +345,7 @@ int ring_conv_launch(const ConvGeom* gs, int n, const long* wm_off, long wm_elem
         RingSub& s = d.sub[d.nsub++];
         s.Hg = g.Hg; s.Wg = g.Wg; s.ooff_h = g.ooff_h; s.ooff_w = g.ooff_w; s.ntaps = g.ntaps; s.KT = g.ntaps * d.spt; s.Kpad = g.Kpad;
         s.wm_off = (int)wm_off[c]; s.tile0 = tiles; s.npix = (int)npix;
-        s.dh_pack = s.dw_pack = 0;
-        for (int k = 0; k < g.ntaps; ++k) {
-            s.dh_pack |= (unsigned)(g.dh[k] + 1) << (2 * k);
-            s.dw_pack |= (unsigned)(g.dw[k] + 1) << (2 * k);
-        }
+        pack_taps(g, &s.dh_pack, &s.dw_pack);
         tiles += (int)((npix + t.bm - 1) / t.bm);
     }
     if (d.nsub == 0) return YOLO_OK;

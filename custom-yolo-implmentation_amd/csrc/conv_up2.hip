@@ -223,23 +223,14 @@ int launch_up2(const Up2Geom& d, const void* src, const void* wm, void* dst, int
     return YOLO_LAUNCH_CHECK();
 }
 
-int up2_mode() {                                              // YOLO_DGRAD2_PATCH=0: never (A/B runs against the gather ring)
-    static const int m = [] {
-        const char* e = getenv("YOLO_DGRAD2_PATCH");
-        return e ? atoi(e) : 1;
-    }();
-    return m;
-}
-
 }  // namespace
 
-// gs[0..4): the four parity classes of one stride-2 data gradient (conv_generic.hip: dgrad_geom).  Returns the variant
-// (0 = not taken, 8 = 8x16 dy pixels x 64 dx channels per workgroup, 16 = 16x16 x 32).
-int up2_conv_variant(const ConvGeom* gs, int dtype) {
+// gs[0..4): the four parity classes of one stride-2 data gradient (conv_select.hip: dgrad_geom): even maps of exactly twice
+// the dy size, 32-channel dy chunks, at least 32 dx channels, no second accumulate source.  variant (up2_conv_launch):
+// 8 = 8x16 dy pixels x 64 dx channels per workgroup, 16 = 16x16 x 32.
+int up2_conv_eligible(const ConvGeom* gs, int dtype) {
     static const int want_taps[4] = {1, 2, 2, 4};
     const ConvGeom& g = gs[0];
-    const int mode = up2_mode();
-    if (mode == 0 || conv_tune().ring > 0 || (conv_tune().halo >= 0 && conv_tune().halo <= 4)) return 0;   // forced-variant tests of the other kernels
     if (dtype != YOLO_BF16 && dtype != YOLO_F16) return 0;
     if ((g.Hd & 1) || (g.Wd & 1) || g.Hs * 2 != g.Hd || g.Ws * 2 != g.Wd || g.Cs % 32 || g.Cd % 8 || g.Cd < 32 || g.lds % 8 || g.ldd % 4) return 0;
     if ((long)g.N * g.Hs * g.Ws * g.lds >= (1L << 30) || (long)g.N * g.Hd * g.Wd >= (1L << 31)) return 0;
@@ -252,10 +243,7 @@ int up2_conv_variant(const ConvGeom* gs, int dtype) {
         for (int t = 0; t < q.ntaps; ++t)
             if (q.dh[t] != t / nw || q.dw[t] != t % nw) return 0;
     }
-    // measured on every stride-2 layer of the step (tools/up2_bench.py, 32 images, ring -> here): 32->64 @320x320 157 -> 98 us,
-    // 128->128 @160 145 -> 107, 256->256 @80 114 -> 88, 128->128 @80 50 -> 35, 256->256 @40 40 -> 35, 256->512 @40 65 -> 56;
-    // with 16-byte stores (round 3): 91 / 99 / 86 / 32 / 36 / 56 us
-    return g.Cd <= 32 ? 16 : 8;
+    return 1;
 }
 
 int up2_conv_launch(const ConvGeom* gs, int variant, const long* wm_off, long wm_elems, const void* src, const void* wm, void* dst,

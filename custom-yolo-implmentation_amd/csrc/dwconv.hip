@@ -8,7 +8,7 @@
 // feed R x 9 x 8 FMAs: 4.5 loads per output for R = 4 instead of 9, horizontal reuse through the vector L1 (lanes of
 // a wave that differ in the column fetch overlapping 1-KB runs).  The 9 x C fp32 taps of the workgroup's channels
 // sit in LDS ([tap][half][channel group][4]: conflict-free 16-byte reads).
-#include "common.h"
+#include "conv_host.h"
 
 namespace {
 

@@ -10,7 +10,7 @@
 // Slabs are combined with fp32 atomics into the packed gradient matrix (64-byte runs along ci).
 #include <cstdio>
 #include <cstdlib>
-#include "common.h"
+#include "conv_host.h"
 
 namespace {
 

@@ -107,7 +107,8 @@ long yolo_conv2d_wgrad_ws_elems(const void* x, int ldx, const void* dy, int ldy,
 int yolo_conv2d_wgrad(const void* x, int ldx, const void* dy, int ldy, float* ws, void* dw_oihw, int dw_dtype, int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, int algo, hipStream_t st);
 /* kernel-selection overrides for tuning runs (tools/conv_tune.py, tools/wg_tune.py) and the variant-forcing parity tests
    (tests/test_gpu_conv_variants.py); process-wide, 0 / -1 = automatic; the training path never calls them.
-   conv: bn in {0, 32, 64, 128}, tap_inner / dma in {-1, 0, 1}, halo in {-1, 0 (gather kernel), 1..4}, ring in {-1, 0 (off), 1},
+   conv: bn in {0, 32, 64, 128}, tap_inner / dma in {-1, 0, 1}, halo in {-1, 0 (gather / ring kernels only), 1..4 (halo variant),
+   5..16 (row-block kernel: the value table is at conv_force in csrc/conv_select.hip)}, ring in {-1, 0 (off), 1},
    bm in {0, 64, 128}, nst in {0, 2, 3, 4} and bk in {0, 32, 64} (ring kernel's pixel tile, ring depth and K-step).  No reference counterpart (model_blocks.py:27). */
 int yolo_conv_tune_set(int bn, int tap_inner, int halo, int dma, int ring, int bm, int nst, int bk);
 int yolo_wgrad_tune_set(int to, int ti, int blocks, int min_per);
@@ -115,7 +116,9 @@ int yolo_wgrad_tune_pf(int pf);
 int yolo_conv_wide_set(int on);   /* conv epilogue stores: 2 = 16-byte, lane-pair exchange by v_permlane16_swap (default); 1 = by ds_bpermute; 0 = 8-byte */
 /* which kernel a forward (mode 0) / data-gradient (mode 1, parity class cls for stride 2) launch of this shape takes:
    kind * 1000 + width, kind 1 = gather MFMA kernel (width = channel tile 32/64/128), 2 = halo MFMA kernel (width = variant 1..4),
-   3 = pipelined ring kernel (width = channel tile, + 500 for 64-pixel tiles), 0 = VALU kernels */
+   3 = pipelined ring kernel (width = channel tile, + 500 for 64-pixel tiles: 3564, 3628), 4 = row-block kernel (width = variant
+   1..4, 6, 7), 5 = stride-2 data-gradient patch kernel (all four classes in one launch; width = variant 8 / 16), 0 = VALU / fp32
+   kernels; -1 = unsupported k / stride.  The launch and this query share one selector (conv_select in csrc/conv_select.hip) */
 int yolo_conv2d_plan(int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int mode, int cls, int dtype);
 /* weight-gradient plan of a shape: to * 1000000 + ti * 100000 + nslab (MFMA path), 0 = other paths */
 long yolo_conv2d_wgrad_plan(int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype);
