@@ -1,7 +1,6 @@
 // HBM-bound NHWC kernels: layout changes, channel copies, BatchNorm (+SiLU, +residual) forward and
 // backward, SPPF max-pool, nearest x2 upsample.  One 16-byte packet per lane wherever the channel
 // count allows it (guide: Guideline 13), fp32 arithmetic, fp32 statistics.
-#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -204,9 +203,8 @@ __global__ void k_add_n(AddSrcs s, T* __restrict__ dst, int ldd, long npix, int 
 }
 
 // ---------------------------------------------------------------------------------------------
-// per-channel reductions over pixels: partial[blk][2][C]
-//   MODE 0: (sum y, sum y^2)                      -- BN batch statistics / bias gradient
-//   MODE 1: (sum dz, sum dz*y), dz = dout*act'(z), z = y*scale+shift   (the finalize kernel centres it)
+// BatchNorm (+SiLU, +residual): per-channel reductions over pixels, finalizes, normalise / gradient passes.
+// The six kernels that touch every element share one row-strided pixel walk (rs_walk).
 // ---------------------------------------------------------------------------------------------
 // sigmoid for the BatchNorm + SiLU kernels: hardware reciprocal (1 ulp) instead of the IEEE division -- the division
 // expands to ~10 VALU instructions per element (v_div_scale x2, v_rcp, 4 fma, v_div_fmas, v_div_fixup) and these kernels
@@ -220,29 +218,71 @@ __device__ __forceinline__ float act_grad(float z, int act) {
 }
 __device__ __forceinline__ float act_fwd(float z, int act) { return act == 0 ? z : z * sigmoid_rcp(z); }
 
-template <typename T, int V, int MODE>
-__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_channel_reduce(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int ldd,
-                                 const float* __restrict__ scale, const float* __restrict__ shift,
-                                 const float* __restrict__ mean, const float* __restrict__ invstd,
-                                 long npix, int C, int act, float* __restrict__ partial) {
+// Row-strided walk: a workgroup is rpb = TPB / tpr pixel rows of tpr lanes; a thread keeps ONE channel group (cg: V
+// channels, whose constants live in registers or LDS; cl: the group's index within the workgroup) and walks pixel rows
+// r, r + rpb, ... of its workgroup's share: no per-element index division.  blockIdx.y covers channel groups beyond tpr.
+// Threads past the last whole row of the workgroup or past the last channel group are not active.
+struct RsThread { int rpb, r, cl, cg; bool active; };
+__device__ __forceinline__ RsThread rs_thread(int tpr, int cv) {
+    RsThread t;
+    t.rpb = TPB / tpr;
+    t.r = threadIdx.x / tpr;
+    t.cl = threadIdx.x - t.r * tpr;
+    t.cg = blockIdx.y * tpr + t.cl;
+    t.active = (t.r < t.rpb) && (t.cg < cv);
+    return t;
+}
+
+// one(p, packet of a, packet of b) for every pixel p of active thread t; without has_b the second tensor is not read.
+// The main loop keeps RS_ROWS independent 16-byte loads per tensor in flight and has no bounds tests; the tail takes
+// one row at a time.  (Start row and step are formed here, after the caller's early exit, not in rs_thread.)
+// The tail runs fewer than RS_ROWS times per thread: left to itself the compiler vectorizes it four wide in the
+// one-element-per-lane backward apply (68 registers instead of 40, a wave less per SIMD), for nothing.
+template <typename T, int V, typename F>
+__device__ __forceinline__ void rs_walk(const RsThread& t, const T* __restrict__ a, int lda, const T* __restrict__ b, int ldb, bool has_b,
+                                        long npix, F one) {
+    const long step = (long)gridDim.x * t.rpb;
+    long p = (long)blockIdx.x * t.rpb + t.r;
+    for (; p + (RS_ROWS - 1) * step < npix; p += RS_ROWS * step) {
+        pack_t<T, V> ra[RS_ROWS], rb[RS_ROWS];
+#pragma unroll
+        for (int k = 0; k < RS_ROWS; ++k) {
+            ra[k] = load_raw<T, V>(a + (p + k * step) * lda + t.cg * V);
+            if (has_b) rb[k] = load_raw<T, V>(b + (p + k * step) * ldb + t.cg * V);
+        }
+#pragma unroll
+        for (int k = 0; k < RS_ROWS; ++k) one(p + k * step, ra[k], rb[k]);
+    }
+#pragma clang loop vectorize(disable)
+    for (; p < npix; p += step) {
+        pack_t<T, V> pa = load_raw<T, V>(a + p * lda + t.cg * V), pb;
+        if (has_b) pb = load_raw<T, V>(b + p * ldb + t.cg * V);
+        one(p, pa, pb);
+    }
+}
+
+// Per-channel sums of one workgroup's pixels, handed to sink(index into a [2][C] row, value):
+//   MODE 0: (sum y, sum y^2)                      -- BN batch statistics / bias gradient
+//   MODE 1: (sum dz, sum dz*y), dz = dout*act'(z), z = y*scale+shift   (raw; the finalize / apply kernel centres the
+//           second sum into sum(dz*yhat) in double)
+// The activation is a template parameter: no per-element select between SiLU and identity.
+template <typename T, int V, int MODE, int ACT, typename Sink>
+__device__ __forceinline__ void channel_sums(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int ldd,
+                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                             long npix, int C, int tpr, Sink sink) {
     __shared__ float red[TPB][2 * V + 1];
     const int cv = C / V;
-    const int tpr = cv < TPB ? cv : TPB;
-    const int rpb = TPB / tpr;
-    const int r = threadIdx.x / tpr;
-    const int cg = blockIdx.y * tpr + (threadIdx.x - r * tpr);
-    const bool active = (r < rpb) && (cg < cv);
+    const RsThread th = rs_thread(tpr, cv);
     float s[V], q[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) s[j] = q[j] = 0.f;
-    if (active) {
+    if (th.active) {
         float sc[V], sh[V];
         if (MODE == 1) {
 #pragma unroll
-            for (int j = 0; j < V; ++j) { sc[j] = scale[cg * V + j]; sh[j] = shift[cg * V + j]; }
+            for (int j = 0; j < V; ++j) { sc[j] = scale[th.cg * V + j]; sh[j] = shift[th.cg * V + j]; }
         }
-        const long step = (long)gridDim.x * rpb;
-        auto one = [&](const pack_t<T, V>& pa, const pack_t<T, V>& pd) {
+        rs_walk<T, V>(th, y, ldy, dout, ldd, MODE == 1, npix, [&](long, const pack_t<T, V>& pa, const pack_t<T, V>& pd) {
             float a[V], d[V];
             unpack<T, V>(pa, a);
             if (MODE == 1) unpack<T, V>(pd, d);
@@ -250,43 +290,35 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
             for (int j = 0; j < V; ++j) {
                 if (MODE == 0) { s[j] += a[j]; q[j] += a[j] * a[j]; }
                 else {
-                    float dz = d[j] * act_grad(a[j] * sc[j] + sh[j], act);
+                    float dz = d[j] * act_grad(a[j] * sc[j] + sh[j], ACT);
                     s[j] += dz;
-                    q[j] += dz * a[j];           // raw; k_bn_bwd_finalize turns it into sum(dz*yhat) in double
+                    q[j] += dz * a[j];
                 }
             }
-        };
-        long p = (long)blockIdx.x * rpb + r;
-        for (; p + (RS_ROWS - 1) * step < npix; p += RS_ROWS * step) {
-            pack_t<T, V> ra[RS_ROWS], rd[RS_ROWS];
-#pragma unroll
-            for (int k = 0; k < RS_ROWS; ++k) {
-                ra[k] = load_raw<T, V>(y + (p + k * step) * ldy + cg * V);
-                if (MODE == 1) rd[k] = load_raw<T, V>(dout + (p + k * step) * ldd + cg * V);
-            }
-#pragma unroll
-            for (int k = 0; k < RS_ROWS; ++k) one(ra[k], rd[k]);
-        }
-        for (; p < npix; p += step) {
-            pack_t<T, V> pa = load_raw<T, V>(y + p * ldy + cg * V), pd;
-            if (MODE == 1) pd = load_raw<T, V>(dout + p * ldd + cg * V);
-            one(pa, pd);
-        }
+        });
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) { red[threadIdx.x][j] = s[j]; red[threadIdx.x][V + j] = q[j]; }
     __syncthreads();
     // one thread per (channel group, value): tpr*2V outputs, each the sum over the workgroup's rpb pixel rows
     // (a single row of threads walking all rows serially cost 10-20 us per workgroup on narrow layers)
-    float* o = partial + (long)blockIdx.x * 2 * C;
     for (int t = threadIdx.x; t < tpr * 2 * V; t += TPB) {
         const int cl = t / (2 * V), j = t - cl * 2 * V;
         float a = 0.f;
 #pragma unroll 8
-        for (int rr = 0; rr < rpb; ++rr) a += red[rr * tpr + cl][j];
+        for (int rr = 0; rr < th.rpb; ++rr) a += red[rr * tpr + cl][j];
         const int cgo = blockIdx.y * tpr + cl;
-        if (cgo < cv) o[(j / V) * C + cgo * V + (j % V)] = a;
+        if (cgo < cv) sink((j / V) * C + cgo * V + (j % V), a);
     }
+}
+
+// deterministic path: workgroup x stores its sums to its own row of partial[gridDim.x][2][C]; a finalize kernel adds the rows
+template <typename T, int V, int MODE, int ACT>
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5, 8)))
+void k_channel_reduce(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int ldd, const float* __restrict__ scale,
+                      const float* __restrict__ shift, long npix, int C, float* __restrict__ partial, int tpr) {
+    float* o = partial + (long)blockIdx.x * 2 * C;
+    channel_sums<T, V, MODE, ACT>(y, ldy, dout, ldd, scale, shift, npix, C, tpr, [&](int i, float a) { o[i] = a; });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -321,94 +353,72 @@ static inline bool pdt_ok(int dt) { return dt == YOLO_F32 || dt == YOLO_BF16 || 
 
 constexpr int BN_REPL = 8;
 
-template <int V>
-__device__ __forceinline__ void fold_replicas(const float* __restrict__ acc, int C, int c0, float (&s)[V], float (&q)[V]) {
-    // issue every replica's loads before the first add: 16 independent packets per thread instead of a
-    // chain of dependent scalar loads (which cost ~14 us per launch)
-    float ts[BN_REPL][V], tq[BN_REPL][V];
+// per-channel constants of a workgroup's cw = tpr*V channels (dynamic LDS): [2][cw] scale, shift in the forward kernel,
+// [5][cw] scale, shift, A, B, D in the backward apply kernels
+extern __shared__ float cf[];
+
+// channel c's two sums over the replicas, in double
+__device__ __forceinline__ void acc_fold(const float* __restrict__ acc, int C, int c, double& s, double& q) {
+    s = 0.0; q = 0.0;
 #pragma unroll
-    for (int r = 0; r < BN_REPL; ++r) {
-        const float* a = acc + (long)r * 2 * C + c0;
-        load_pack<float, V>(a, ts[r]);
-        load_pack<float, V>(a + C, tq[r]);
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-        s[j] = ((ts[0][j] + ts[1][j]) + (ts[2][j] + ts[3][j])) + ((ts[4][j] + ts[5][j]) + (ts[6][j] + ts[7][j]));
-        q[j] = ((tq[0][j] + tq[1][j]) + (tq[2][j] + tq[3][j])) + ((tq[4][j] + tq[5][j]) + (tq[6][j] + tq[7][j]));
-    }
+    for (int r = 0; r < BN_REPL; ++r) { s += acc[(long)r * 2 * C + c]; q += acc[(long)r * 2 * C + C + c]; }
 }
 
-// MODE 0: acc += (sum y, sum y^2).  MODE 1: acc += (sum dz, sum dz*yhat) with z = (y-mean)*invstd*gamma + beta
+// default path: the same sums, added into replica (workgroup index mod BN_REPL) of acc.  scale / shift of MODE 1 are the
+// forward's.
 template <typename T, int V, int MODE, int ACT>
-__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_channel_acc(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int ldd,
-                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                              const float* __restrict__ mean, const float* __restrict__ invstd,
-                              long npix, int C, int act, float* __restrict__ acc, int tpr, int rev) {
-    const long pix_b = rev ? npix - 1 : 0, pix_d = rev ? -1 : 1;   // traversal direction (see bn_rev())
-#define PIX(p_) (pix_b + pix_d * (p_))
-
-    __shared__ float red[TPB][2 * V + 1];
-    const int cv = C / V;
-    const int rpb = TPB / tpr;
-    const int r = threadIdx.x / tpr;
-    const int cg = blockIdx.y * tpr + (threadIdx.x - r * tpr);
-    const bool active = (r < rpb) && (cg < cv);
-    float s[V], q[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) s[j] = q[j] = 0.f;
-    if (active) {
-        float sc[V], sh[V];
-        if (MODE == 1) {                                    // MODE 1: gamma / beta carry the forward's scale / shift
-#pragma unroll
-            for (int j = 0; j < V; ++j) { sc[j] = gamma[cg * V + j]; sh[j] = beta[cg * V + j]; }
-        }
-        const long step = (long)gridDim.x * rpb;
-        auto one = [&](const pack_t<T, V>& pa, const pack_t<T, V>& pd) {
-            float a[V], d[V];
-            unpack<T, V>(pa, a);
-            if (MODE == 1) unpack<T, V>(pd, d);
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                if (MODE == 0) { s[j] += a[j]; q[j] += a[j] * a[j]; }
-                else {
-                    float dz = d[j] * act_grad(a[j] * sc[j] + sh[j], ACT);
-                    s[j] += dz;
-                    q[j] += dz * a[j];            // raw; the apply kernel centres it
-                }
-            }
-        };
-        long p = (long)blockIdx.x * rpb + r;
-        for (; p + (RS_ROWS - 1) * step < npix; p += RS_ROWS * step) {
-            pack_t<T, V> ra[RS_ROWS], rd[RS_ROWS];
-#pragma unroll
-            for (int k = 0; k < RS_ROWS; ++k) {
-                ra[k] = load_raw<T, V>(y + PIX(p + k * step) * ldy + cg * V);
-                if (MODE == 1) rd[k] = load_raw<T, V>(dout + PIX(p + k * step) * ldd + cg * V);
-            }
-#pragma unroll
-            for (int k = 0; k < RS_ROWS; ++k) one(ra[k], rd[k]);
-        }
-        for (; p < npix; p += step) {
-            pack_t<T, V> pa = load_raw<T, V>(y + PIX(p) * ldy + cg * V), pd;
-            if (MODE == 1) pd = load_raw<T, V>(dout + PIX(p) * ldd + cg * V);
-            one(pa, pd);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) { red[threadIdx.x][j] = s[j]; red[threadIdx.x][V + j] = q[j]; }
-    __syncthreads();
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5, 8)))
+void k_channel_acc(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int ldd, const float* __restrict__ scale,
+                   const float* __restrict__ shift, long npix, int C, float* __restrict__ acc, int tpr) {
     float* o = acc + (long)(blockIdx.x % BN_REPL) * 2 * C;
-    for (int t = threadIdx.x; t < tpr * 2 * V; t += TPB) {
-        const int cl = t / (2 * V), j = t - cl * 2 * V;
-        float a = 0.f;
-#pragma unroll 8
-        for (int rr = 0; rr < rpb; ++rr) a += red[rr * tpr + cl][j];
-        const int cgo = blockIdx.y * tpr + cl;
-        if (cgo < cv) atomicAdd(o + (j / V) * C + cgo * V + (j % V), a);
+    channel_sums<T, V, MODE, ACT>(y, ldy, dout, ldd, scale, shift, npix, C, tpr, [&](int i, float a) { atomicAdd(o + i, a); });
+}
+
+// Statistics -> coefficients of one channel, the only place this arithmetic is written.  Training-mode forward: (sum y,
+// sum y^2) in double -> batch mean / biased variance (clamped at 0) -> invstd, scale, shift, and the unbiased variance the
+// running statistics take (torch.nn.BatchNorm2d semantics).
+struct BnFwdCoef { float mean, invstd, scale, shift, unbiased; };
+__device__ __forceinline__ BnFwdCoef bn_fwd_coef(double s, double q, float count, float eps, float gamma, float beta) {
+    const double m = s / count;
+    double var = q / count - m * m;
+    if (var < 0.0) var = 0.0;
+    BnFwdCoef k;
+    k.invstd = (float)(1.0 / sqrt(var + (double)eps));
+    k.mean = (float)m;
+    k.scale = gamma * k.invstd;
+    k.shift = beta - (float)m * k.scale;
+    k.unbiased = (float)(count > 1.f ? var * (count / (count - 1.0)) : var);
+    return k;
+}
+// ... and their publication: the four saved vectors, the running statistics updated with momentum
+__device__ __forceinline__ void bn_fwd_publish(const BnFwdCoef& k, int c, float momentum, float* __restrict__ mean,
+                                               float* __restrict__ invstd, float* __restrict__ scale,
+                                               float* __restrict__ shift, const PIo& rmean, const PIo& rvar) {
+    mean[c] = k.mean;
+    invstd[c] = k.invstd;
+    scale[c] = k.scale;
+    shift[c] = k.shift;
+    if (rmean.p) {
+        rmean.st(c, (1.f - momentum) * rmean.ld(c) + momentum * k.mean);
+        rvar.st(c, (1.f - momentum) * rvar.ld(c) + momentum * k.unbiased);
     }
 }
-#undef PIX
+// Backward: (sum dz, sum dz*y) in double -> dbeta = sum dz, dgamma = sum dz*yhat = invstd*(sum dz*y - mean*sum dz), and
+// dy = k0*(dz - c1 - yhat*c2), yhat = (y-mean)*invstd  ==  A*dz + B*y + D  (three constants per channel)
+struct BnBwdCoef { float dbeta, dgamma, A, B, D; };
+__device__ __forceinline__ BnBwdCoef bn_bwd_coef(double s, double q, float count, const PIn& gamma, const float* __restrict__ mean,
+                                                 const float* __restrict__ invstd, int c) {
+    const double is = invstd[c], mu = mean[c];
+    q = is * (q - mu * s);
+    const double k0 = (double)gamma.ld(c) * is, c1 = s / count, c2 = q / count;
+    BnBwdCoef k;
+    k.dbeta = (float)s;
+    k.dgamma = (float)q;
+    k.A = (float)k0;
+    k.B = (float)(-k0 * c2 * is);
+    k.D = (float)(-k0 * c1 + k0 * c2 * mu * is);
+    return k;
+}
 
 // acc[8][2][C] -> mean, invstd, scale, shift (+ running statistics): one thread per channel, 16 loads
 __global__ void k_bn_finalize_acc(const float* __restrict__ acc, float count, int C, const void* __restrict__ gamma_,
@@ -418,111 +428,82 @@ __global__ void k_bn_finalize_acc(const float* __restrict__ acc, float count, in
     const PIn gamma{gamma_, pdt}; const PIn beta{beta_, pdt}; const PIo rmean{rmean_, bdt}, rvar{rvar_, bdt};
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double s = 0.0, q = 0.0;
+    double s, q;
+    acc_fold(acc, C, c, s, q);
+    bn_fwd_publish(bn_fwd_coef(s, q, count, eps, gamma.ld(c), beta.ld(c)), c, momentum, mean, invstd, scale, shift, rmean, rvar);
+}
+
+// out = act(y*scale + shift) (+ res) over the pixels of thread th, scale / shift of its channels in registers
+template <typename T, int V>
+__device__ __forceinline__ void bn_act_fwd_rows(const RsThread& th, const T* __restrict__ y, int ldy, const T* __restrict__ res,
+                                                int ldr, T* __restrict__ out, int ldo, long npix, const float (&sc)[V],
+                                                const float (&sh)[V], int act) {
+    const bool has_res = res;
+    rs_walk<T, V>(th, y, ldy, res, ldr, has_res, npix, [&](long p, const pack_t<T, V>& pa, const pack_t<T, V>& pt) {
+        float a[V], t[V];
+        unpack<T, V>(pa, a);
+        if (has_res) unpack<T, V>(pt, t);
 #pragma unroll
-    for (int r = 0; r < BN_REPL; ++r) { s += acc[(long)r * 2 * C + c]; q += acc[(long)r * 2 * C + C + c]; }
-    const double m = s / count;
-    double var = q / count - m * m;
-    if (var < 0.0) var = 0.0;
-    const float is = (float)(1.0 / sqrt(var + (double)eps));
-    mean[c] = (float)m;
-    invstd[c] = is;
-    const float g = gamma.ld(c) * is;
-    scale[c] = g;
-    shift[c] = beta.ld(c) - (float)m * g;
-    if (rmean.p) {
-        const double unb = count > 1.f ? var * (count / (count - 1.0)) : var;
-        rmean.st(c, (1.f - momentum) * rmean.ld(c) + momentum * (float)m);
-        rvar.st(c, (1.f - momentum) * rvar.ld(c) + momentum * (float)unb);
-    }
+        for (int j = 0; j < V; ++j) a[j] = act_fwd(a[j] * sc[j] + sh[j], act) + (has_res ? t[j] : 0.f);
+        store_pack<T, V>(out + p * ldo + th.cg * V, a);
+    });
+}
+
+// dy = A*dz + B*y + D, dz = dout*act'(y*scale + shift), over the pixels of thread th.  The five per-channel constants of
+// the workgroup's channels sit in LDS (cf: [5][cw]) and are read at use: forty live coefficient registers per thread
+// would halve the occupancy of a pure streaming kernel.
+template <typename T, int V>
+__device__ __forceinline__ void bn_act_bwd_rows(const RsThread& th, const T* __restrict__ dout, int ldd, const T* __restrict__ y,
+                                                int ldy, T* __restrict__ dy, int lddy, long npix, int cw, int act) {
+    const float* my = cf + th.cl * V;
+    rs_walk<T, V>(th, y, ldy, dout, ldd, true, npix, [&](long p, const pack_t<T, V>& pa, const pack_t<T, V>& pd) {
+        float a[V], d[V];
+        unpack<T, V>(pa, a);
+        unpack<T, V>(pd, d);
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            d[j] = my[2 * cw + j] * (d[j] * act_grad(a[j] * my[j] + my[cw + j], act)) + my[3 * cw + j] * a[j] + my[4 * cw + j];
+        store_pack<T, V>(dy + p * lddy + th.cg * V, d);
+    });
 }
 
 // out = act(BN_batch(y)) (+ res) with the finalize folded in: every workgroup derives scale / shift of ITS channels
 // from the statistics accumulator acc[8][2][C] (coalesced loads spread over the workgroup, then LDS); workgroup row 0
-// also publishes mean / invstd / scale / shift and updates the running statistics.  Same arithmetic as
-// k_bn_finalize_acc.
+// also publishes mean / invstd / scale / shift and updates the running statistics.
 template <typename T, int V, int ACT>
 __global__ __launch_bounds__(TPB) void k_bn_act_fwd_train(const T* __restrict__ y, int ldy, const float* __restrict__ acc, float count,
                         const void* __restrict__ gamma_, const void* __restrict__ beta_, void* __restrict__ rmean_,
                         void* __restrict__ rvar_, float momentum, float eps, float* __restrict__ mean_out,
                         float* __restrict__ invstd_out, float* __restrict__ scale_out, float* __restrict__ shift_out,
-                        const T* __restrict__ res, int ldr, T* __restrict__ out, int ldo, long npix, int C, int act, int tpr, int pdt, int bdt, int rev) {
-    const long pix_b = rev ? npix - 1 : 0, pix_d = rev ? -1 : 1;   // traversal direction (see bn_rev())
-#define PIX(p_) (pix_b + pix_d * (p_))
-
+                        const T* __restrict__ res, int ldr, T* __restrict__ out, int ldo, long npix, int C, int tpr, int pdt, int bdt) {
     const PIn gamma{gamma_, pdt}; const PIn beta{beta_, pdt}; const PIo rmean{rmean_, bdt}, rvar{rvar_, bdt};
-    extern __shared__ float cf[];                            // [2][cw]: scale, shift of this workgroup's channels
-    const int cv = C / V;
-    const int rpb = TPB / tpr;
     const int cw = tpr * V;
     for (int t = threadIdx.x; t < cw; t += TPB) {
         const int c = blockIdx.y * cw + t;
         float g = 0.f, sh0 = 0.f;
         if (c < C) {
-            double s = 0.0, q = 0.0;
-#pragma unroll
-            for (int r = 0; r < BN_REPL; ++r) { s += acc[(long)r * 2 * C + c]; q += acc[(long)r * 2 * C + C + c]; }
-            const double m = s / count;
-            double var = q / count - m * m;
-            if (var < 0.0) var = 0.0;
-            const float is = (float)(1.0 / sqrt(var + (double)eps));
-            g = gamma.ld(c) * is;
-            sh0 = beta.ld(c) - (float)m * g;
-            if (blockIdx.x == 0) {
-                mean_out[c] = (float)m;
-                invstd_out[c] = is;
-                scale_out[c] = g;
-                shift_out[c] = sh0;
-                if (rmean.p) {
-                    const double unb = count > 1.f ? var * (count / (count - 1.0)) : var;
-                    rmean.st(c, (1.f - momentum) * rmean.ld(c) + momentum * (float)m);
-                    rvar.st(c, (1.f - momentum) * rvar.ld(c) + momentum * (float)unb);
-                }
-            }
+            double s, q;
+            acc_fold(acc, C, c, s, q);
+            const BnFwdCoef k = bn_fwd_coef(s, q, count, eps, gamma.ld(c), beta.ld(c));
+            g = k.scale;
+            sh0 = k.shift;
+            if (blockIdx.x == 0) bn_fwd_publish(k, c, momentum, mean_out, invstd_out, scale_out, shift_out, rmean, rvar);
         }
         cf[t] = g;
         cf[cw + t] = sh0;
     }
     __syncthreads();
-    const int r = threadIdx.x / tpr;
-    const int cl = threadIdx.x - r * tpr;
-    const int cg = blockIdx.y * tpr + cl;
-    if (r >= rpb || cg >= cv) return;
+    const RsThread th = rs_thread(tpr, C / V);
+    if (!th.active) return;
     float sc[V], sh[V];
 #pragma unroll
-    for (int j = 0; j < V; ++j) { sc[j] = cf[cl * V + j]; sh[j] = cf[cw + cl * V + j]; }
-    const long step = (long)gridDim.x * rpb;
-    auto one = [&](long p, const pack_t<T, V>& pa, const pack_t<T, V>& pt) {
-        float a[V], t[V];
-        unpack<T, V>(pa, a);
-        if (res) unpack<T, V>(pt, t);
-#pragma unroll
-        for (int j = 0; j < V; ++j) a[j] = act_fwd(a[j] * sc[j] + sh[j], ACT) + (res ? t[j] : 0.f);
-        store_pack<T, V>(out + PIX(p) * ldo + cg * V, a);
-    };
-    long p = (long)blockIdx.x * rpb + r;
-    for (; p + (RS_ROWS - 1) * step < npix; p += RS_ROWS * step) {
-        pack_t<T, V> ra[RS_ROWS], rt[RS_ROWS];
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) {
-            ra[k] = load_raw<T, V>(y + PIX(p + k * step) * ldy + cg * V);
-            if (res) rt[k] = load_raw<T, V>(res + PIX(p + k * step) * ldr + cg * V);
-        }
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) one(p + k * step, ra[k], rt[k]);
-    }
-    for (; p < npix; p += step) {
-        pack_t<T, V> pa = load_raw<T, V>(y + PIX(p) * ldy + cg * V), pt;
-        if (res) pt = load_raw<T, V>(res + PIX(p) * ldr + cg * V);
-        one(p, pa, pt);
-    }
+    for (int j = 0; j < V; ++j) { sc[j] = cf[th.cl * V + j]; sh[j] = cf[cw + th.cl * V + j]; }
+    bn_act_fwd_rows<T, V>(th, y, ldy, res, ldr, out, ldo, npix, sc, sh, ACT);
 }
-#undef PIX
 
 // dy = A*dz + B*y + D with the backward finalize folded in: acc[8][2][C] holds (sum dz, sum dz*y) of the reduction
-// kernel (float atomics into 8 replicas); every workgroup folds the replicas of ITS channels, centres the second
-// sum (sum dz*yhat = invstd*(sum dz*y - mean*sum dz)) and derives the five constants into LDS; workgroup row 0
-// also writes dgamma / dbeta.  Same arithmetic as k_bn_bwd_finalize (double).
+// kernel (float atomics into 8 replicas); every workgroup folds the replicas of ITS channels and derives the five
+// constants into LDS; workgroup row 0 also writes dgamma / dbeta.
 template <typename T, int V, int ACT>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5, 8)))
 void k_bn_act_bwd_apply_train(const T* __restrict__ dout, int ldd, const T* __restrict__ y, int ldy,
@@ -530,64 +511,27 @@ void k_bn_act_bwd_apply_train(const T* __restrict__ dout, int ldd, const T* __re
                               const void* __restrict__ gamma_, const float* __restrict__ mean,
                               const float* __restrict__ invstd, const float* __restrict__ acc, float count,
                               void* __restrict__ dgamma_, void* __restrict__ dbeta_, T* __restrict__ dy, int lddy,
-                              long npix, int C, int act, int tpr, int pdt, int rev) {
-    const long pix_b = rev ? npix - 1 : 0, pix_d = rev ? -1 : 1;   // traversal direction (see bn_rev())
-#define PIX(p_) (pix_b + pix_d * (p_))
-
+                              long npix, int C, int tpr, int pdt) {
     const PIn gamma{gamma_, pdt}; const PIo dgamma{dgamma_, pdt}, dbeta{dbeta_, pdt};
-    extern __shared__ float cf[];                            // [5][cw]: scale, shift, A, B, D
-    const int cv = C / V;
-    const int rpb = TPB / tpr;
     const int cw = tpr * V;
     for (int t = threadIdx.x; t < cw; t += TPB) {
         const int c = blockIdx.y * cw + t;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f;
+        float v0 = 0.f, v1 = 0.f;
+        BnBwdCoef k{0.f, 0.f, 0.f, 0.f, 0.f};
         if (c < C) {
-            double s = 0.0, q = 0.0;
-#pragma unroll
-            for (int r = 0; r < BN_REPL; ++r) { s += acc[(long)r * 2 * C + c]; q += acc[(long)r * 2 * C + C + c]; }
-            const double is = invstd[c], mu = mean[c];
-            q = is * (q - mu * s);                           // sum(dz*yhat)
-            const double k0 = (double)gamma.ld(c) * is, c1 = s / count, c2 = q / count;
+            double s, q;
+            acc_fold(acc, C, c, s, q);
+            k = bn_bwd_coef(s, q, count, gamma, mean, invstd, c);
             v0 = scale[c]; v1 = shift[c];
-            v2 = (float)k0;
-            v3 = (float)(-k0 * c2 * is);
-            v4 = (float)(-k0 * c1 + k0 * c2 * mu * is);
-            if (blockIdx.x == 0) { dbeta.st(c, (float)s); dgamma.st(c, (float)q); }
+            if (blockIdx.x == 0) { dbeta.st(c, k.dbeta); dgamma.st(c, k.dgamma); }
         }
-        cf[t] = v0; cf[cw + t] = v1; cf[2 * cw + t] = v2; cf[3 * cw + t] = v3; cf[4 * cw + t] = v4;
+        cf[t] = v0; cf[cw + t] = v1; cf[2 * cw + t] = k.A; cf[3 * cw + t] = k.B; cf[4 * cw + t] = k.D;
     }
     __syncthreads();
-    const int r = threadIdx.x / tpr;
-    const int cl = threadIdx.x - r * tpr;
-    const int cg = blockIdx.y * tpr + cl;
-    if (r >= rpb || cg >= cv) return;
-    const float* my = cf + cl * V;
-    const long step = (long)gridDim.x * rpb;
-    auto one = [&](long p, const pack_t<T, V>& pa, const pack_t<T, V>& pd) {
-        float a[V], d[V];
-        unpack<T, V>(pa, a);
-        unpack<T, V>(pd, d);
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-            d[j] = my[2 * cw + j] * (d[j] * act_grad(a[j] * my[j] + my[cw + j], ACT)) + my[3 * cw + j] * a[j] + my[4 * cw + j];
-        store_pack<T, V>(dy + PIX(p) * lddy + cg * V, d);
-    };
-    long p = (long)blockIdx.x * rpb + r;
-    for (; p + (RS_ROWS - 1) * step < npix; p += RS_ROWS * step) {
-        pack_t<T, V> ra[RS_ROWS], rd[RS_ROWS];
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) {
-            ra[k] = load_raw<T, V>(y + PIX(p + k * step) * ldy + cg * V);
-            rd[k] = load_raw<T, V>(dout + PIX(p + k * step) * ldd + cg * V);
-        }
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) one(p + k * step, ra[k], rd[k]);
-    }
-    for (; p < npix; p += step)
-        one(p, load_raw<T, V>(y + PIX(p) * ldy + cg * V), load_raw<T, V>(dout + PIX(p) * ldd + cg * V));
+    const RsThread th = rs_thread(tpr, C / V);
+    if (!th.active) return;
+    bn_act_bwd_rows<T, V>(th, dout, ldd, y, ldy, dy, lddy, npix, cw, ACT);
 }
-#undef PIX
 
 // Finalize kernels run as (32 channels x 32 parts) 1024-thread workgroups: part j sums partial blocks
 // j, j+32, ... of its channel (128-byte coalesced rows), LDS combines the 32 parts; the thread with
@@ -614,8 +558,7 @@ __device__ __forceinline__ int fin_reduce(const float* __restrict__ partial, int
     return c;
 }
 
-// finalize for training-mode BN: batch mean / biased var -> invstd, scale, shift; running stats
-// updated with momentum and the unbiased variance (torch.nn.BatchNorm2d semantics).
+// finalize for training-mode BN, from the partial rows of k_channel_reduce
 __global__ void k_bn_finalize(const float* __restrict__ partial, int nblk, float count, int C,
                               const void* __restrict__ gamma_, const void* __restrict__ beta_,
                               void* __restrict__ rmean_, void* __restrict__ rvar_, float momentum, float eps,
@@ -625,20 +568,7 @@ __global__ void k_bn_finalize(const float* __restrict__ partial, int nblk, float
     double s, q;
     const int c = fin_reduce(partial, nblk, C, s, q);
     if (c < 0) return;
-    double m = s / count;
-    double var = q / count - m * m;
-    if (var < 0.0) var = 0.0;
-    float is = (float)(1.0 / sqrt(var + (double)eps));
-    mean[c] = (float)m;
-    invstd[c] = is;
-    float g = gamma.ld(c) * is;
-    scale[c] = g;
-    shift[c] = beta.ld(c) - (float)m * g;
-    if (rmean.p) {
-        double unb = count > 1.f ? var * (count / (count - 1.0)) : var;
-        rmean.st(c, (1.f - momentum) * rmean.ld(c) + momentum * (float)m);
-        rvar.st(c, (1.f - momentum) * rvar.ld(c) + momentum * (float)unb);
-    }
+    bn_fwd_publish(bn_fwd_coef(s, q, count, eps, gamma.ld(c), beta.ld(c)), c, momentum, mean, invstd, scale, shift, rmean, rvar);
 }
 
 __global__ void k_bn_eval_coeffs(const void* __restrict__ gamma_, const void* __restrict__ beta_,
@@ -652,7 +582,7 @@ __global__ void k_bn_eval_coeffs(const void* __restrict__ gamma_, const void* __
     shift[c] = beta.ld(c) - rmean.ld(c) * g;
 }
 
-// backward finalize: dgamma = sum dz*yhat, dbeta = sum dz, coef = [gamma*invstd, dbeta/m, dgamma/m]
+// backward finalize, from the partial rows of k_channel_reduce: dgamma, dbeta, coef = [A, B, D] of bn_bwd_coef
 __global__ void k_bn_bwd_finalize(const float* __restrict__ partial, int nblk, float count, int C,
                                   const void* __restrict__ gamma_, const float* __restrict__ mean, const float* __restrict__ invstd,
                                   void* __restrict__ dgamma_, void* __restrict__ dbeta_, float* __restrict__ coef, int pdt) {
@@ -660,14 +590,12 @@ __global__ void k_bn_bwd_finalize(const float* __restrict__ partial, int nblk, f
     double s, q;
     const int c = fin_reduce(partial, nblk, C, s, q);
     if (c < 0) return;
-    q = (double)invstd[c] * (q - (double)mean[c] * s);      // partial rows hold sum(dz*y): -> sum(dz*yhat)
-    dbeta.st(c, (float)s);
-    dgamma.st(c, (float)q);
-    // dy = k0*(dz - c1 - yhat*c2), yhat = (y-mean)*invstd  ==  A*dz + B*y + D  (three constants per channel)
-    const double k0 = (double)gamma.ld(c) * invstd[c], c1 = s / count, c2 = q / count;
-    coef[c] = (float)k0;
-    coef[C + c] = (float)(-k0 * c2 * invstd[c]);
-    coef[2 * C + c] = (float)(-k0 * c1 + k0 * c2 * (double)mean[c] * invstd[c]);
+    const BnBwdCoef k = bn_bwd_coef(s, q, count, gamma, mean, invstd, c);
+    dbeta.st(c, k.dbeta);
+    dgamma.st(c, k.dgamma);
+    coef[c] = k.A;
+    coef[C + c] = k.B;
+    coef[2 * C + c] = k.D;
 }
 
 __global__ void k_sum_finalize(const float* __restrict__ partial, int nblk, int C, float* __restrict__ out) {
@@ -680,56 +608,22 @@ __global__ void k_sum_finalize(const float* __restrict__ partial, int nblk, int 
 template <typename T, int V>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bn_act_fwd(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
                              const float* __restrict__ shift, const T* __restrict__ res, int ldr,
-                             T* __restrict__ out, int ldo, long npix, int cv, int act) {
-    // row-strided: a thread keeps ONE channel group (its scale/shift live in registers) and walks pixels;
-    // no per-element index division, RS_ROWS pixels (loads) in flight per iteration
-    const int tpr = cv < TPB ? cv : TPB, rpb = TPB / tpr;
-    const int r = threadIdx.x / tpr;
-    const int cg = blockIdx.y * tpr + (threadIdx.x - r * tpr);
-    if (r >= rpb || cg >= cv) return;
+                             T* __restrict__ out, int ldo, long npix, int cv, int act, int tpr) {
+    const RsThread th = rs_thread(tpr, cv);
+    if (!th.active) return;
     float sc[V], sh[V];
 #pragma unroll
-    for (int j = 0; j < V; ++j) { sc[j] = scale[cg * V + j]; sh[j] = shift[cg * V + j]; }
-    const long step = (long)gridDim.x * rpb;
-    auto one = [&](long p, const pack_t<T, V>& pa, const pack_t<T, V>& pt) {
-        float a[V], t[V];
-        unpack<T, V>(pa, a);
-        if (res) unpack<T, V>(pt, t);
-#pragma unroll
-        for (int j = 0; j < V; ++j) a[j] = act_fwd(a[j] * sc[j] + sh[j], act) + (res ? t[j] : 0.f);
-        store_pack<T, V>(out + p * ldo + cg * V, a);
-    };
-    long p = (long)blockIdx.x * rpb + r;
-    for (; p + (RS_ROWS - 1) * step < npix; p += RS_ROWS * step) {       // RS_ROWS loads in flight, no bounds tests
-        pack_t<T, V> ra[RS_ROWS], rt[RS_ROWS];
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) {
-            ra[k] = load_raw<T, V>(y + (p + k * step) * ldy + cg * V);
-            if (res) rt[k] = load_raw<T, V>(res + (p + k * step) * ldr + cg * V);
-        }
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) one(p + k * step, ra[k], rt[k]);
-    }
-    for (; p < npix; p += step) {
-        pack_t<T, V> pa = load_raw<T, V>(y + p * ldy + cg * V), pt;
-        if (res) pt = load_raw<T, V>(res + p * ldr + cg * V);
-        one(p, pa, pt);
-    }
+    for (int j = 0; j < V; ++j) { sc[j] = scale[th.cg * V + j]; sh[j] = shift[th.cg * V + j]; }
+    bn_act_fwd_rows<T, V>(th, y, ldy, res, ldr, out, ldo, npix, sc, sh, act);
 }
 
-// dy = k0*(dz - c1 - yhat*c2);  eval-style (coef == null): dy = scale*dz
+// dy = A*dz + B*y + D with (A, B, D) = coef rows from k_bn_bwd_finalize; eval-style, frozen statistics (coef == null):
+// (scale, 0, 0), dy = scale*dz
 template <typename T, int V>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_bn_act_bwd_apply(const T* __restrict__ dout, int ldd, const T* __restrict__ y, int ldy,
                                    const float* __restrict__ scale, const float* __restrict__ shift,
-                                   const float* __restrict__ mean, const float* __restrict__ invstd,
                                    const float* __restrict__ coef, T* __restrict__ dy, int lddy,
-                                   long npix, int C, int act) {
-    // dy = A*dz + B*y + D with (A, B, D) = coef rows from k_bn_bwd_finalize; frozen statistics: (scale, 0, 0).
-    // The five per-channel constants of the workgroup's channels sit in LDS ([5][tpr*V] floats, dynamic) and are
-    // read at use: forty live coefficient registers per thread would halve the occupancy of a pure streaming kernel.
-    extern __shared__ float cf[];
-    const int cv = C / V;
-    const int tpr = cv < TPB ? cv : TPB, rpb = TPB / tpr;
+                                   long npix, int C, int act, int tpr) {
     const int cw = tpr * V;                                  // channels of this workgroup
     for (int t = threadIdx.x; t < cw; t += TPB) {
         const int c = blockIdx.y * cw + t;
@@ -741,34 +635,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         cf[4 * cw + t] = (in && coef) ? coef[2 * C + c] : 0.f;
     }
     __syncthreads();
-    const int r = threadIdx.x / tpr;
-    const int cl = threadIdx.x - r * tpr;
-    const int cg = blockIdx.y * tpr + cl;
-    if (r >= rpb || cg >= cv) return;
-    const float* my = cf + cl * V;
-    const long step = (long)gridDim.x * rpb;
-    auto one = [&](long p, const pack_t<T, V>& pa, const pack_t<T, V>& pd) {
-        float a[V], d[V];
-        unpack<T, V>(pa, a);
-        unpack<T, V>(pd, d);
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-            d[j] = my[2 * cw + j] * (d[j] * act_grad(a[j] * my[j] + my[cw + j], act)) + my[3 * cw + j] * a[j] + my[4 * cw + j];
-        store_pack<T, V>(dy + p * lddy + cg * V, d);
-    };
-    long p = (long)blockIdx.x * rpb + r;
-    for (; p + (RS_ROWS - 1) * step < npix; p += RS_ROWS * step) {
-        pack_t<T, V> ra[RS_ROWS], rd[RS_ROWS];
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) {
-            ra[k] = load_raw<T, V>(y + (p + k * step) * ldy + cg * V);
-            rd[k] = load_raw<T, V>(dout + (p + k * step) * ldd + cg * V);
-        }
-#pragma unroll
-        for (int k = 0; k < RS_ROWS; ++k) one(p + k * step, ra[k], rd[k]);
-    }
-    for (; p < npix; p += step)
-        one(p, load_raw<T, V>(y + p * ldy + cg * V), load_raw<T, V>(dout + p * ldd + cg * V));
+    const RsThread th = rs_thread(tpr, C / V);
+    if (!th.active) return;
+    bn_act_bwd_rows<T, V>(th, dout, ldd, y, ldy, dy, lddy, npix, cw, act);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -931,45 +800,33 @@ __global__ void k_upsample2x_bwd(const T* __restrict__ dout, int ldd, T* __restr
     }
 }
 
-// grid of a row-strided kernel: x walks pixel rows (RS_ROWS per thread per iteration), y covers channel groups >
-// 256.  At most RS_MAXBLK workgroups (all resident at once: no partial last round), and every workgroup gets
-// the same number of iterations.
-inline dim3 rs_grid(long npix, int cv) {
-    int tpr = cv < TPB ? cv : TPB, rpb = TPB / tpr;
+// Workgroups along x of a row-strided kernel with tpr lanes per row: a workgroup takes RS_ROWS * rpb pixel rows per
+// iteration; at most max(cap, cap_min) workgroups, and every workgroup gets the same number of iterations.
+inline long rs_blocks(long npix, int tpr, long cap, long cap_min) {
+    const int rpb = TPB / tpr;
     long units = (npix + (long)RS_ROWS * rpb - 1) / ((long)RS_ROWS * rpb);
     if (units < 1) units = 1;
-    long iters = (units + RS_MAXBLK - 1) / RS_MAXBLK;
-    long gx = (units + iters - 1) / iters;
-    return dim3((unsigned)gx, (unsigned)ceil_div(cv, tpr));
+    if (cap < cap_min) cap = cap_min;
+    const long iters = (units + cap - 1) / cap;
+    return (units + iters - 1) / iters;
 }
 
-// Plan of the training-path BatchNorm kernels (the accumulator forms above).  Every workgroup pays a prologue /
+// Launch plan of a row-strided kernel: x walks pixel rows, y covers the channel groups beyond one row.  At most RS_MAXBLK
+// workgroups (all resident at once: no partial last round).
+// narrow: the plan of the training-path BatchNorm kernels (the accumulator forms above).  Every workgroup pays a prologue /
 // epilogue per channel it covers (16 accumulator loads + double arithmetic, or an LDS reduction + atomics), whatever
 // the tensor's size: on a 20x20 map with 512 channels a workgroup that spans all channels (64 lanes per row) and two
 // rows per lane fetched 32 KB of accumulators for 8 KB of activations.  Wide layers on small maps therefore use
 // 16-lane rows (256-byte segments, channel groups on blockIdx.y): measured 12.1 -> 10.2 us forward and 30.6 -> 24.6 us
 // backward for 512 channels at 20x20 x 32 images; capping the workgroup count as well made the 64..128-channel
 // layers slower and is not done.
-// Traversal direction of the three training-mode BatchNorm passes, one bit each (1 = from the last pixel down): bit 0 the
-// forward normalise pass, bit 1 the backward reduction, bit 2 the backward apply.  A pass that walks a tensor in the
-// direction OPPOSITE to the pass that last touched it meets that pass's most recent lines first -- still in the L2s / the
-// 256 MB Infinity Cache -- instead of evicting them on its way to them.  YOLO_BN_REV overrides (A/B runs).
-static inline int bn_rev() {
-    static const int v = [] { const char* e = getenv("YOLO_BN_REV"); return e ? atoi(e) : 0; }();
-    return v;
-}
 struct RsPlan { int tpr; dim3 grid; };
-inline RsPlan rs_plan(long npix, int cv) {
+inline RsPlan rs_plan(long npix, int cv, bool narrow) {
     RsPlan p;
     p.tpr = cv < TPB ? cv : TPB;
-    if (p.tpr > 16 && npix * cv <= (1L << 20)) p.tpr = 16;   // <= 8 M elements
-    const int rpb = TPB / p.tpr, gy = ceil_div(cv, p.tpr);
-    long units = (npix + (long)RS_ROWS * rpb - 1) / ((long)RS_ROWS * rpb);
-    if (units < 1) units = 1;
-    long gmax = RS_MAXBLK / gy;
-    if (gmax < 8) gmax = 8;
-    const long iters = (units + gmax - 1) / gmax;
-    p.grid = dim3((unsigned)((units + iters - 1) / iters), (unsigned)gy);
+    if (narrow && p.tpr > 16 && npix * cv <= (1L << 20)) p.tpr = 16;   // <= 8 M elements
+    const int gy = ceil_div(cv, p.tpr);
+    p.grid = dim3((unsigned)rs_blocks(npix, p.tpr, narrow ? RS_MAXBLK / gy : RS_MAXBLK, 8), (unsigned)gy);
     return p;
 }
 
@@ -1000,6 +857,14 @@ int nhwc_to_ncm_out(const void* src, int ld, void* dst, int dst_dtype, long sn, 
 #define PICK_V(T, ok, ...)                                       \
     if (ok) { constexpr int V = vec_of<T>::N; __VA_ARGS__; }     \
     else    { constexpr int V = 1; __VA_ARGS__; }
+// the activation as a template parameter: no per-element select between SiLU and identity
+#define PICK_ACT(act, ...)                                       \
+    if (act) { constexpr int ACT = 1; __VA_ARGS__; }             \
+    else     { constexpr int ACT = 0; __VA_ARGS__; }
+// the instantiations of the channel reductions: MODE 0 has no activation
+#define PICK_MODE_ACT(mode, act, ...)                            \
+    if ((mode) == 0) { constexpr int MODE = 0, ACT = 0; __VA_ARGS__; } \
+    else { constexpr int MODE = 1; PICK_ACT(act, __VA_ARGS__) }
 
 extern "C" {
 
@@ -1120,40 +985,28 @@ int yolo_add_n(const void* s0, int ld0, const void* s1, int ld1, const void* s2,
 // number of partial blocks yolo_bn_stats / yolo_bn_act_bwd_reduce will write for this problem
 int yolo_reduce_nblk(long npix, int C) {
     // one partial row per workgroup; same balanced sizing as the other row-strided kernels (<= 1024 workgroups)
-    int cv = C / 8 > 0 ? C / 8 : 1;
-    int tpr = cv < TPB ? cv : TPB, rpb = TPB / tpr;
-    long units = (npix + (long)RS_ROWS * rpb - 1) / ((long)RS_ROWS * rpb);
-    if (units < 1) units = 1;
+    const int cv = C / 8 > 0 ? C / 8 : 1;
     long cap = npix / 32;              // keep the partial rows (2*C floats each) well below the tensor's own bytes
     if (cap > 1024) cap = 1024;
-    if (cap < 1) cap = 1;
-    long iters = (units + cap - 1) / cap;
-    return (int)((units + iters - 1) / iters);
+    return (int)rs_blocks(npix, cv < TPB ? cv : TPB, cap, 1);
 }
 
 static int launch_reduce(int mode, const void* y, int ldy, const void* dout, int ldd, const float* scale,
-                         const float* shift, const float* mean, const float* invstd, long npix, int C, int act,
-                         int dtype, float* partial, int nblk, hipStream_t st) {
+                         const float* shift, long npix, int C, int act, int dtype, float* partial, int nblk, hipStream_t st) {
     if (nblk != yolo_reduce_nblk(npix, C)) return YOLO_ERR_ARG;
     YOLO_DISPATCH_T(dtype, {
         bool ok = vec_ok<T>(y, ldy, C) && (mode == 0 || vec_ok<T>(dout, ldd, C));
         PICK_V(T, ok, {
-            int cv = C / V;
-            int tpr = cv < TPB ? cv : TPB;
-            dim3 g(nblk, ceil_div(cv, tpr));
-            if (mode == 0)
-                hipLaunchKernelGGL((k_channel_reduce<T, V, 0>), g, dim3(TPB), 0, st, (const T*)y, ldy, (const T*)nullptr,
-                                   0, scale, shift, mean, invstd, npix, C, act, partial);
-            else
-                hipLaunchKernelGGL((k_channel_reduce<T, V, 1>), g, dim3(TPB), 0, st, (const T*)y, ldy, (const T*)dout,
-                                   ldd, scale, shift, mean, invstd, npix, C, act, partial);
+            const RsPlan pl = rs_plan(npix, C / V, false);
+            PICK_MODE_ACT(mode, act, hipLaunchKernelGGL((k_channel_reduce<T, V, MODE, ACT>), dim3(nblk, pl.grid.y), dim3(TPB), 0, st,
+                                                        (const T*)y, ldy, (const T*)dout, ldd, scale, shift, npix, C, partial, pl.tpr));
         });
     });
     return YOLO_LAUNCH_CHECK();
 }
 
 int yolo_bn_stats(const void* y, int ldy, long npix, int C, int dtype, float* partial, int nblk, hipStream_t st) {
-    return launch_reduce(0, y, ldy, nullptr, 0, nullptr, nullptr, nullptr, nullptr, npix, C, 0, dtype, partial, nblk, st);
+    return launch_reduce(0, y, ldy, nullptr, 0, nullptr, nullptr, npix, C, 0, dtype, partial, nblk, st);
 }
 
 int yolo_bn_finalize(const float* partial, int nblk, long count, int C, const void* gamma, const void* beta,
@@ -1183,9 +1036,9 @@ int yolo_bn_act_fwd(const void* y, int ldy, const float* scale, const float* shi
     YOLO_DISPATCH_T(dtype, {
         bool ok = vec_ok<T>(y, ldy, C) && vec_ok<T>(out, ldout, C) && (!res || vec_ok<T>(res, ldres, C));
         PICK_V(T, ok, {
-            int cv = C / V;
-            hipLaunchKernelGGL((k_bn_act_fwd<T, V>), rs_grid(npix, cv), dim3(TPB), 0, st, (const T*)y, ldy, scale,
-                               shift, (const T*)res, ldres, (T*)out, ldout, npix, cv, act);
+            const RsPlan pl = rs_plan(npix, C / V, false);
+            hipLaunchKernelGGL((k_bn_act_fwd<T, V>), pl.grid, dim3(TPB), 0, st, (const T*)y, ldy, scale,
+                               shift, (const T*)res, ldres, (T*)out, ldout, npix, C / V, act, pl.tpr);
         });
     });
     return YOLO_LAUNCH_CHECK();
@@ -1194,7 +1047,7 @@ int yolo_bn_act_fwd(const void* y, int ldy, const float* scale, const float* shi
 int yolo_bn_act_bwd_reduce(const void* dout, int ldd, const void* y, int ldy, const float* scale, const float* shift,
                            const float* mean, const float* invstd, long npix, int C, int act, int dtype,
                            float* partial, int nblk, hipStream_t st) {
-    return launch_reduce(1, y, ldy, dout, ldd, scale, shift, mean, invstd, npix, C, act, dtype, partial, nblk, st);
+    return launch_reduce(1, y, ldy, dout, ldd, scale, shift, npix, C, act, dtype, partial, nblk, st);
 }
 
 int yolo_bn_bwd_finalize(const float* partial, int nblk, long count, int C, const void* gamma, const float* mean,
@@ -1211,10 +1064,9 @@ int yolo_bn_act_bwd_apply(const void* dout, int ldd, const void* y, int ldy, con
     YOLO_DISPATCH_T(dtype, {
         bool ok = vec_ok<T>(y, ldy, C) && vec_ok<T>(dout, ldd, C) && vec_ok<T>(dy, lddy, C);
         PICK_V(T, ok, {
-            int cv = C / V;
-            const int tpr = cv < TPB ? cv : TPB;
-            hipLaunchKernelGGL((k_bn_act_bwd_apply<T, V>), rs_grid(npix, cv), dim3(TPB), 5 * tpr * V * sizeof(float), st, (const T*)dout,
-                               ldd, (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, npix, C, act);
+            const RsPlan pl = rs_plan(npix, C / V, false);
+            hipLaunchKernelGGL((k_bn_act_bwd_apply<T, V>), pl.grid, dim3(TPB), 5 * pl.tpr * V * sizeof(float), st, (const T*)dout,
+                               ldd, (const T*)y, ldy, scale, shift, coef, (T*)dy, lddy, npix, C, act, pl.tpr);
         });
     });
     return YOLO_LAUNCH_CHECK();
@@ -1223,29 +1075,21 @@ int yolo_bn_act_bwd_apply(const void* dout, int ldd, const void* y, int ldy, con
 // ---- accumulator form (no finalize launches).  acc: fp32 [YOLO_BN_REPL = 8][2][C], zeroed by the caller.
 int yolo_bn_acc_elems(int C) { return BN_REPL * 2 * C; }
 
-static int launch_acc(int mode, const void* y, int ldy, const void* dout, int ldd, const float* gamma, const float* beta,
-                      const float* mean, const float* invstd, long npix, int C, int act, int dtype, float* acc,
-                      hipStream_t st) {
+static int launch_acc(int mode, const void* y, int ldy, const void* dout, int ldd, const float* scale, const float* shift,
+                      long npix, int C, int act, int dtype, float* acc, hipStream_t st) {
     YOLO_DISPATCH_T(dtype, {
         bool ok = vec_ok<T>(y, ldy, C) && (mode == 0 || vec_ok<T>(dout, ldd, C));
         PICK_V(T, ok, {
-            const RsPlan pl = rs_plan(npix, C / V);
-            if (mode == 0)
-                hipLaunchKernelGGL((k_channel_acc<T, V, 0, 0>), pl.grid, dim3(TPB), 0, st, (const T*)y, ldy, (const T*)nullptr, 0,
-                                   gamma, beta, mean, invstd, npix, C, act, acc, pl.tpr, (bn_rev() >> (mode ? 1 : 0)) & 1);
-            else if (act)     // the activation is a template parameter: no per-element select between SiLU and identity
-                hipLaunchKernelGGL((k_channel_acc<T, V, 1, 1>), pl.grid, dim3(TPB), 0, st, (const T*)y, ldy, (const T*)dout, ldd,
-                                   gamma, beta, mean, invstd, npix, C, act, acc, pl.tpr, (bn_rev() >> (mode ? 1 : 0)) & 1);
-            else
-                hipLaunchKernelGGL((k_channel_acc<T, V, 1, 0>), pl.grid, dim3(TPB), 0, st, (const T*)y, ldy, (const T*)dout, ldd,
-                                   gamma, beta, mean, invstd, npix, C, act, acc, pl.tpr, (bn_rev() >> (mode ? 1 : 0)) & 1);
+            const RsPlan pl = rs_plan(npix, C / V, true);
+            PICK_MODE_ACT(mode, act, hipLaunchKernelGGL((k_channel_acc<T, V, MODE, ACT>), pl.grid, dim3(TPB), 0, st, (const T*)y, ldy,
+                                                        (const T*)dout, ldd, scale, shift, npix, C, acc, pl.tpr));
         });
     });
     return YOLO_LAUNCH_CHECK();
 }
 
 int yolo_bn_stats_acc(const void* y, int ldy, long npix, int C, int dtype, float* acc, hipStream_t st) {
-    return launch_acc(0, y, ldy, nullptr, 0, nullptr, nullptr, nullptr, nullptr, npix, C, 0, dtype, acc, st);
+    return launch_acc(0, y, ldy, nullptr, 0, nullptr, nullptr, npix, C, 0, dtype, acc, st);
 }
 
 int yolo_bn_finalize_acc(const float* acc, long count, int C, const void* gamma, const void* beta, void* running_mean,
@@ -1265,15 +1109,10 @@ int yolo_bn_act_fwd_train(const void* y, int ldy, const float* acc, long count, 
     YOLO_DISPATCH_T(dtype, {
         bool ok = vec_ok<T>(y, ldy, C) && vec_ok<T>(out, ldout, C) && (!res || vec_ok<T>(res, ldres, C));
         PICK_V(T, ok, {
-            const RsPlan pl = rs_plan(npix, C / V);
-            if (act)
-                hipLaunchKernelGGL((k_bn_act_fwd_train<T, V, 1>), pl.grid, dim3(TPB), 2 * pl.tpr * V * sizeof(float), st,
+            const RsPlan pl = rs_plan(npix, C / V, true);
+            PICK_ACT(act, hipLaunchKernelGGL((k_bn_act_fwd_train<T, V, ACT>), pl.grid, dim3(TPB), 2 * pl.tpr * V * sizeof(float), st,
                                (const T*)y, ldy, acc, (float)count, gamma, beta, running_mean, running_var, momentum, eps,
-                               mean, invstd, scale, shift, (const T*)res, ldres, (T*)out, ldout, npix, C, act, pl.tpr, pdtype, bdtype, bn_rev() & 1);
-            else
-                hipLaunchKernelGGL((k_bn_act_fwd_train<T, V, 0>), pl.grid, dim3(TPB), 2 * pl.tpr * V * sizeof(float), st,
-                               (const T*)y, ldy, acc, (float)count, gamma, beta, running_mean, running_var, momentum, eps,
-                               mean, invstd, scale, shift, (const T*)res, ldres, (T*)out, ldout, npix, C, act, pl.tpr, pdtype, bdtype, bn_rev() & 1);
+                               mean, invstd, scale, shift, (const T*)res, ldres, (T*)out, ldout, npix, C, pl.tpr, pdtype, bdtype));
         });
     });
     return YOLO_LAUNCH_CHECK();
@@ -1282,7 +1121,7 @@ int yolo_bn_act_fwd_train(const void* y, int ldy, const float* acc, long count, 
 // backward pass 1 with atomics: acc[8][2][C] (zeroed by the caller) += (sum dz, sum dz*y), dz = dout*act'(y*scale+shift)
 int yolo_bn_bwd_reduce_acc(const void* dout, int ldd, const void* y, int ldy, const float* scale, const float* shift,
                            long npix, int C, int act, int dtype, float* acc, hipStream_t st) {
-    return launch_acc(1, y, ldy, dout, ldd, scale, shift, nullptr, nullptr, npix, C, act, dtype, acc, st);
+    return launch_acc(1, y, ldy, dout, ldd, scale, shift, npix, C, act, dtype, acc, st);
 }
 
 int yolo_bn_act_bwd_apply_train(const void* dout, int ldd, const void* y, int ldy, const float* scale, const float* shift,
@@ -1293,15 +1132,10 @@ int yolo_bn_act_bwd_apply_train(const void* dout, int ldd, const void* y, int ld
     YOLO_DISPATCH_T(dtype, {
         bool ok = vec_ok<T>(y, ldy, C) && vec_ok<T>(dout, ldd, C) && vec_ok<T>(dy, lddy, C);
         PICK_V(T, ok, {
-            const RsPlan pl = rs_plan(npix, C / V);
-            if (act)
-                hipLaunchKernelGGL((k_bn_act_bwd_apply_train<T, V, 1>), pl.grid, dim3(TPB), 5 * pl.tpr * V * sizeof(float), st,
+            const RsPlan pl = rs_plan(npix, C / V, true);
+            PICK_ACT(act, hipLaunchKernelGGL((k_bn_act_bwd_apply_train<T, V, ACT>), pl.grid, dim3(TPB), 5 * pl.tpr * V * sizeof(float), st,
                                (const T*)dout, ldd, (const T*)y, ldy, scale, shift, gamma, mean, invstd, acc, (float)count,
-                               dgamma, dbeta, (T*)dy, lddy, npix, C, act, pl.tpr, pdtype, (bn_rev() >> 2) & 1);
-            else
-                hipLaunchKernelGGL((k_bn_act_bwd_apply_train<T, V, 0>), pl.grid, dim3(TPB), 5 * pl.tpr * V * sizeof(float), st,
-                               (const T*)dout, ldd, (const T*)y, ldy, scale, shift, gamma, mean, invstd, acc, (float)count,
-                               dgamma, dbeta, (T*)dy, lddy, npix, C, act, pl.tpr, pdtype, (bn_rev() >> 2) & 1);
+                               dgamma, dbeta, (T*)dy, lddy, npix, C, pl.tpr, pdtype));
         });
     });
     return YOLO_LAUNCH_CHECK();

@@ -45,7 +45,6 @@ def deterministic_stats():
 
 
 _SIDE = {}
-FOLD_BN_FINALIZE = True     # BN scale/shift are derived in the prologue of the activation kernel (no finalize launch)
 OVERLAP_WGRAD = True        # run a conv's weight gradient on a side stream, concurrently with its data gradient
 FWD_STREAM = None           # see ConvBnAct.forward
 HEAD_TWO_STREAMS = os.environ.get("YOLO_HEAD_STREAMS", "1") == "1"       # Head.forward; 0 for A/B runs
@@ -365,17 +364,13 @@ class ConvBnAct(torch.autograd.Function):
             res = _as_nhwc(res, T)
         acc_b = None
         if training:
-            if FOLD_BN_FINALIZE and BnArena.current is not None and not deterministic:
+            if BnArena.current is not None and not deterministic:
                 acc_b = BnArena.current.take(cout)          # zeroed with the forward statistics; used by the backward
             if deterministic:
                 mean, invstd, scale, shift = ops.bn_train_stats(y, gamma, beta, rm, rv, momentum, eps)
                 out = ops.bn_act_fwd(y, scale, shift, act, res, out)
-            elif FOLD_BN_FINALIZE:
+            else:       # BN scale/shift are derived in the prologue of the activation kernel (no finalize launch)
                 out, mean, invstd, scale, shift = ops.bn_act_fwd_train(y, acc_f, gamma, beta, rm, rv, momentum, eps, act, res, out)
-            else:
-                count = y.shape[0] * y.shape[2] * y.shape[3]
-                mean, invstd, scale, shift = ops.bn_finalize_acc(acc_f, count, gamma, beta, rm, rv, momentum, eps)
-                out = ops.bn_act_fwd(y, scale, shift, act, res, out)
         else:
             mean = invstd = None
             scale, shift = ops.bn_eval_coeffs(gamma, beta, rm, rv, eps)

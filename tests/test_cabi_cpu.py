@@ -1,6 +1,7 @@
 """No-GPU checks of the drop-in boundary: the shared library loads, exports exactly what include/yolo_hip.h
 declares, and its host-only queries answer (no kernel is launched here)."""
 import ctypes
+import json
 import os
 import re
 
@@ -32,6 +33,15 @@ def test_host_side_queries():
     assert lib.query("yolo_reduce_nblk", 10, 8) == 1 and lib.query("yolo_reduce_nblk", 10 ** 7, 8) <= 2048
     assert lib.query("yolo_nms_capacity", 8400, 80, 0) == 8400 and lib.query("yolo_nms_capacity", 33600, 80, 1) == 131072
     assert lib.query("yolo_loss_workspace_bytes", 2, 2100, 20) >= 2 * 2100 * 16 + 80
+
+
+def test_reduce_nblk_matches_the_recorded_table():
+    """the balanced grid sizing of the row-strided reductions, pinned to what the library answered before the sizing
+    moved into one function (tests/golden/gen_reduce_nblk_table.py)"""
+    t = json.load(open(os.path.join(ROOT, "tests", "golden", "reduce_nblk_table.json")))
+    assert len(t["npix"]) == 11 and len(t["C"]) == 12
+    got = [[lib.query("yolo_reduce_nblk", p, c) for c in t["C"]] for p in t["npix"]]
+    assert got == t["nblk"]
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

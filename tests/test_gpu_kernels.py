@@ -399,6 +399,46 @@ def test_bn_accumulator_path_with_conv_epilogue_stats(dtype, cin, cout, h, w, k,
     check(dg, dg_r, torch.float32, "dgamma", mult=20.0), check(db, db_r, torch.float32, "dbeta", mult=20.0)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("act", [0, 1])
+@pytest.mark.parametrize("n,c,h,w,pad,with_res", [(3, 6, 11, 13, 0, True), (3, 24, 11, 13, 8, False), (3, 24, 11, 13, 16, False),
+                                                  (3, 264, 11, 13, 0, True), (2, 264, 110, 100, 0, False)])
+def test_bn_accumulator_path_row_walk_shapes(dtype, act, n, c, h, w, pad, with_res):
+    """bn_stats_acc -> bn_act_fwd_train -> bn_act_bwd_train at op level (no conv), on the shapes at which the pixel walk the
+    accumulator kernels share can go wrong: one element per lane with 6 lanes per row (threads 252..255 past the last row);
+    a row stride that is not the channel count (a slice 4 channels into its buffer, which only fp32 can read in 16-byte packets,
+    and one 8 channels in, which every dtype can); 16-lane rows with a partly filled last channel group and 429 pixels (some
+    threads run the main loop, some only the tail); 22 000 pixels (688 units against a cap of 682 workgroups: more than one
+    main-loop iteration per thread)."""
+    o = ops()
+    y, dout = nhwc((rnd(n, c, h, w, seed=70) * 1.5 + 0.3).to(dtype), pad), nhwc(rnd(n, c, h, w, seed=72).to(dtype), pad)
+    res = nhwc(rnd(n, c, h, w, seed=71).to(dtype)) if with_res else None
+    gamma, beta = 1 + 0.1 * rnd(c, seed=73), 0.1 * rnd(c, seed=74)
+    rm, rv = 0.1 * rnd(c, seed=75), 1 + 0.1 * rnd(c, seed=76).abs()
+    rm_g, rv_g = rm.clone().to(DEV), rv.clone().to(DEV)
+    wide = 100.0 if dtype != torch.float32 else 4.0
+    y_g = dev(y)
+    acc_f, acc_b = o.bn_acc_new(c, DEV), o.bn_acc_new(c, DEV)
+    ref_f, ref_b = torch.zeros(8 * 2 * c), torch.zeros(8 * 2 * c)
+    o.bn_stats_acc(y_g, acc_f)
+    emu.bn_stats_acc(y, ref_f)
+    sums, sums_r = acc_f.view(8, 2, c).sum(0).cpu(), ref_f.view(8, 2, c).sum(0)
+    check(sums[0], sums_r[0], torch.float32, "sum", mult=20.0, scale=float(y.float().abs().sum((0, 2, 3)).max()))
+    check(sums[1], sums_r[1], torch.float32, "sumsq", mult=20.0)
+    out, mean, invstd, scale, shift = o.bn_act_fwd_train(y_g, acc_f, gamma.to(DEV), beta.to(DEV), rm_g, rv_g, 0.03, 1e-3, act, dev(res))
+    out_r, mean_r, invstd_r, scale_r, shift_r = emu.bn_act_fwd_train(y, ref_f, gamma, beta, rm, rv, 0.03, 1e-3, act, res)
+    check(scale, scale_r, torch.float32, "scale", mult=wide, scale=max(1.0, float(scale_r.abs().max())))
+    check(shift, shift_r, torch.float32, "shift", mult=wide, scale=max(1.0, float(shift_r.abs().max())))
+    check(mean, mean_r, torch.float32, "mean", mult=50.0 if dtype != torch.float32 else 4.0, scale=float(y.float().abs().max()))
+    check(invstd, invstd_r, torch.float32, "invstd", mult=wide)
+    check(out, out_r, dtype, "bn_act_fwd_train", mult=2.0)
+    check(rm_g, rm, torch.float32, "running_mean", mult=50.0), check(rv_g, rv, torch.float32, "running_var", mult=100.0)
+    dy, dg, db = o.bn_act_bwd_train(dev(dout), y_g, scale, shift, mean, invstd, gamma.to(DEV), act, acc_b)
+    dy_r, dg_r, db_r = emu.bn_act_bwd_train(dout, y, scale.cpu(), shift.cpu(), mean.cpu(), invstd.cpu(), gamma, act, ref_b)
+    check(dy, dy_r, dtype, "bn bwd dy", mult=2.0)
+    check(dg, dg_r, torch.float32, "dgamma", mult=20.0), check(db, db_r, torch.float32, "dbeta", mult=20.0)
+
+
 # ------------------------------------------------------------------------------------------ pool / upsample
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 def test_maxpool5_and_upsample(dtype):
