@@ -8,6 +8,12 @@
 // Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) rides on the same table: k_grad_sqnorm
 // leaves one partial sum of squares per chunk, k_clip_finalize turns them into [total_norm, coef] in device memory and
 // k_adamw multiplies the gradient by coef in flight, next to the unscale (the .grad tensors are not modified).
+// Exponential moving average of the weights (the ModelEMA of the YOLOv5 / v8 recipes; the reference has none) rides in
+// k_adamw too: a record may carry an fp32 shadow `e` and a control block ectl = [decay, tau, updates] (doubles, device
+// memory, one per parameter group); with d = tau > 0 ? decay * (1 - exp(-updates / tau)) : decay the kernel leaves
+// e = d*e + (1-d)*w behind, w being the parameter AS STORED.  k_adamw_tick counts `updates` next to `step`, so a step
+// skipped on found_inf moves neither the shadows nor the ramp.  k_ema_lerp is the same average over tensors that the
+// optimizer does not step (BatchNorm running statistics): one more launch over a table of its own.
 #include "common.h"
 
 struct AdamJob {
@@ -18,6 +24,8 @@ struct AdamJob {
     long n;             // elements
     long cstart;        // first 4096-element chunk (= workgroup) of this job
     int p_dtype, g_dtype;
+    float* e;           // EMA shadow of p (fp32), or null
+    double* ectl;       // EMA control block of the group [decay, tau, updates], or null
 };
 
 namespace {
@@ -46,9 +54,22 @@ __device__ __forceinline__ void adam_elem(float& p, float gg, float& m, float& v
     p = __fsub_rn(__fmul_rn(p, decay), __fdiv_rn(__fmul_rn(step_size, m), denom));
 }
 
-// step += 1 unless the scaler found an overflow (one thread; the main kernel reads the updated value)
-__global__ void k_adamw_tick(float* __restrict__ step, const float* __restrict__ found_inf) {
-    if (found_inf == nullptr || *found_inf == 0.f) *step += 1.f;
+// The EMA coefficients of one launch from the control block: df = fl(d), omd = fl(1 - d), both rounded from the double d.
+__device__ __forceinline__ void ema_coef(const double* ectl, float& df, float& omd) {
+    const double decay = ectl[0], tau = ectl[1], updates = ectl[2];
+    const double d = tau > 0.0 ? decay * (1.0 - exp(-updates / tau)) : decay;
+    df = (float)d;
+    omd = (float)(1.0 - d);
+}
+
+// step += 1 (and the group's EMA update count, found through the first record) unless the scaler found an overflow
+// (one thread; the main kernel reads the updated values)
+__global__ void k_adamw_tick(float* __restrict__ step, const float* __restrict__ found_inf, const AdamJob* __restrict__ jobs) {
+    if (found_inf == nullptr || *found_inf == 0.f) {
+        *step += 1.f;
+        double* ectl = jobs[0].ectl;
+        if (ectl != nullptr) ectl[2] += 1.0;
+    }
 }
 
 // hyper = [lr, beta1, beta2, eps, weight_decay] as DOUBLES: 1 - beta and the bias corrections are formed in double
@@ -58,7 +79,7 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
                                                const float* __restrict__ found_inf, const float* __restrict__ clip) {
     if (found_inf != nullptr && *found_inf != 0.f) return;
     __shared__ int sj;
-    __shared__ float sc[7];                     // b1, 1-b1, b2, 1-b2, step_size, 1/sqrt(bc2), decay
+    __shared__ float sc[9];                     // b1, 1-b1, b2, 1-b2, step_size, 1/sqrt(bc2), decay, ema d, ema 1-d
     if (threadIdx.x == 0) {
         int lo = 0, hi = njobs - 1;
         while (lo < hi) {                       // last job with cstart <= blockIdx.x
@@ -70,17 +91,21 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
         const double bc1 = 1.0 - pow(b1d, t), bc2 = 1.0 - pow(b2d, t);
         sc[0] = (float)b1d; sc[1] = (float)(1.0 - b1d); sc[2] = (float)b2d; sc[3] = (float)(1.0 - b2d);
         sc[4] = (float)(lr / bc1); sc[5] = (float)sqrt(bc2); sc[6] = (float)(1.0 - lr * wd);
+        sc[7] = 0.f; sc[8] = 0.f;
+        if (jobs[lo].e != nullptr && jobs[lo].ectl != nullptr) ema_coef(jobs[lo].ectl, sc[7], sc[8]);
     }
     __syncthreads();
     const AdamJob j = jobs[sj];
     const float b1 = sc[0], omb1 = sc[1], b2 = sc[2], omb2 = sc[3], step_size = sc[4], bc2s = sc[5], decay = sc[6];
     const float eps = (float)hyper[3];
+    const float df = sc[7], omd = sc[8];
+    float* const ema = j.ectl != nullptr ? j.e : nullptr;
     float gs = grad_scale ? 1.f / *grad_scale : 1.f;            // GradScaler: gradients arrive multiplied by the scale
     if (clip != nullptr) gs *= clip[2];                         // clip state = [max_norm, total_norm, coef]; x * 1.f is x
     const long base = ((long)blockIdx.x - j.cstart) * CHUNK;
     if (j.p_dtype == YOLO_F32 && j.g_dtype == YOLO_F32 && (j.n & 3) == 0 &&
         ((reinterpret_cast<uintptr_t>(j.p) | reinterpret_cast<uintptr_t>(j.g) | reinterpret_cast<uintptr_t>(j.m) |
-          reinterpret_cast<uintptr_t>(j.v)) & 15) == 0) {
+          reinterpret_cast<uintptr_t>(j.v) | reinterpret_cast<uintptr_t>(ema)) & 15) == 0) {
         // the common case: fp32 master weights and gradients, 16-byte packets
         for (long i = base + threadIdx.x * 4L; i < base + CHUNK && i < j.n; i += 256 * 4) {
             float4 p = *reinterpret_cast<float4*>((float*)j.p + i);
@@ -92,6 +117,13 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
             *reinterpret_cast<float4*>((float*)j.p + i) = p;
             *reinterpret_cast<float4*>(j.m + i) = m;
             *reinterpret_cast<float4*>(j.v + i) = v;
+            if (ema != nullptr) {
+                float4 e = *reinterpret_cast<float4*>(ema + i);
+                float* ep = &e.x;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ep[k] = __fmaf_rn(df, ep[k], __fmul_rn(omd, pp[k]));
+                *reinterpret_cast<float4*>(ema + i) = e;
+            }
         }
         return;
     }
@@ -101,7 +133,39 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
         j.m[i] = m;
         j.v[i] = v;
         st_any(j.p, j.p_dtype, i, pv);
+        if (ema != nullptr) {
+            // the parameter as stored: a bf16 / f16 parameter's rounded value, so the average is one of the observable weights
+            const float w = j.p_dtype == YOLO_F32 ? pv : j.p_dtype == YOLO_BF16 ? to_f<bf16_t>(from_f<bf16_t>(pv))
+                                                                                 : to_f<f16_t>(from_f<f16_t>(pv));
+            ema[i] = __fmaf_rn(df, ema[i], __fmul_rn(omd, w));
+        }
     }
+}
+
+// e = d*e + (1-d)*p over a job table whose records carry p (read only) and e, g / m / v null: the tensors the optimizer
+// does not step.  Launched after the AdamW launches of the step, so `updates` already counts this step; skip_flag non-zero
+// (the step was skipped on overflow) leaves every shadow as it is.
+__global__ __launch_bounds__(256) void k_ema_lerp(const AdamJob* __restrict__ jobs, int njobs, const double* __restrict__ ectl,
+                                                  const float* __restrict__ skip_flag) {
+    if (skip_flag != nullptr && *skip_flag != 0.f) return;
+    __shared__ int sj;
+    __shared__ float sc[2];
+    if (threadIdx.x == 0) {
+        int lo = 0, hi = njobs - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (jobs[mid].cstart <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+        }
+        sj = lo;
+        ema_coef(ectl, sc[0], sc[1]);
+    }
+    __syncthreads();
+    const AdamJob j = jobs[sj];
+    const float df = sc[0], omd = sc[1];
+    if (j.e == nullptr) return;
+    const long base = ((long)blockIdx.x - j.cstart) * CHUNK;
+    for (long i = base + threadIdx.x; i < base + CHUNK && i < j.n; i += 256)
+        j.e[i] = __fmaf_rn(df, j.e[i], __fmul_rn(omd, ld_any(j.p, j.p_dtype, i)));
 }
 
 // ---- global gradient norm (torch.nn.utils.clip_grad_norm_, norm_type 2; the reference's config.yaml carries
@@ -239,6 +303,15 @@ int yolo_adamw_job_fill(void* jobs_host, int index, void* p, int p_dtype, const 
     if (n < 0) return YOLO_ERR_ARG;
     AdamJob& j = ((AdamJob*)jobs_host)[index];
     j.p = p; j.g = g; j.m = m; j.v = v; j.n = n; j.cstart = 0; j.p_dtype = p_dtype; j.g_dtype = g_dtype;
+    j.e = nullptr; j.ectl = nullptr;
+    return YOLO_OK;
+}
+
+// the EMA shadow and control block of record `index` (after yolo_adamw_job_fill, which clears both); null = no EMA
+int yolo_adamw_job_set_ema(void* jobs_host, int index, float* ema, double* ema_ctl) {
+    if (index < 0) return YOLO_ERR_ARG;
+    AdamJob& j = ((AdamJob*)jobs_host)[index];
+    j.e = ema; j.ectl = ema_ctl;
     return YOLO_OK;
 }
 
@@ -265,7 +338,7 @@ long yolo_adamw_jobs_finalize(void* jobs_host, int njobs) {
 int yolo_adamw_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale,
                     const float* found_inf, hipStream_t st) {
     if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
-    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, found_inf);
+    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, found_inf, (const AdamJob*)jobs_dev);
     hipLaunchKernelGGL(k_adamw, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step,
                        grad_scale, found_inf, (const float*)nullptr);
     return YOLO_LAUNCH_CHECK();
@@ -278,7 +351,7 @@ int yolo_adamw_amp_step(const void* jobs_dev, int njobs, long nchunks, const dou
     if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
     if (!(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f) || growth_interval < 1) return YOLO_ERR_ARG;
     hipLaunchKernelGGL(k_found_inf, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, amp_state + 1);
-    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, amp_state + 1);
+    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, amp_state + 1, (const AdamJob*)jobs_dev);
     hipLaunchKernelGGL(k_adamw, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step,
                        amp_state, amp_state + 1, (const float*)nullptr);
     hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, st, amp_state, growth_tracker, growth_factor, backoff_factor, growth_interval);
@@ -306,7 +379,7 @@ int yolo_adamw_clip_step(const void* jobs_dev, int njobs, long nchunks, const do
                          const float* found_inf, const float* clip_state, hipStream_t st) {
     if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
     if (clip_state == nullptr) return YOLO_ERR_ARG;
-    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, found_inf);
+    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, found_inf, (const AdamJob*)jobs_dev);
     hipLaunchKernelGGL(k_adamw, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step,
                        grad_scale, found_inf, clip_state);
     return YOLO_LAUNCH_CHECK();
@@ -316,6 +389,15 @@ int yolo_amp_update_scale(float* amp_state, int* growth_tracker, float growth_fa
                           hipStream_t st) {
     if (!(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f) || growth_interval < 1) return YOLO_ERR_ARG;
     hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, st, amp_state, growth_tracker, growth_factor, backoff_factor, growth_interval);
+    return YOLO_LAUNCH_CHECK();
+}
+
+// EMA of the tensors the optimizer does not step (BatchNorm running statistics): records with p and e (g / m / v null), the
+// chunk grid of the AdamW launches, d from ema_ctl as in k_adamw; nothing moves when *skip_flag != 0.
+int yolo_ema_lerp(const void* jobs_dev, int njobs, long nchunks, const double* ema_ctl, const float* skip_flag, hipStream_t st) {
+    if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
+    if (ema_ctl == nullptr) return YOLO_ERR_ARG;
+    hipLaunchKernelGGL(k_ema_lerp, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, ema_ctl, skip_flag);
     return YOLO_LAUNCH_CHECK();
 }
 

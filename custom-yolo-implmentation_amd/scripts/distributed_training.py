@@ -91,9 +91,18 @@ def main(args):
         optimizer, scheduler = get_optimizer(model=model, lr=tr_cfg["learning_rate"], weight_decay=tr_cfg["weight_decay"],
                                              patience=tr_cfg["learning_rate_patience"], factor=tr_cfg["learning_rate_factor"],
                                              max_grad_norm=max_grad_norm)
+        # optional key `training.ema: {decay: ..., tau: ...}`: an exponential moving average of the weights kept inside the
+        # optimizer step; validation runs on it and checkpoints carry it (absent = off; the reference has no EMA)
+        ema = None
+        ema_cfg = tr_cfg.get("ema", None)
+        if ema_cfg is not None:
+            if args.mode != "ddp":
+                raise ValueError(f"training.ema is not supported in {args.mode} mode; use ddp mode or remove the key")
+            from src.training.ema import ModelEMA
+            ema = ModelEMA(model, optimizer, decay=ema_cfg.get("decay", 0.9999), tau=ema_cfg.get("tau", 2000.0))
         if args.load_from_checkpoint:
             path = find_latest_checkpoint(ckpt_dir)
-            initial_epoch = load_checkpoint(model, optimizer, path, map_location=args.device)
+            initial_epoch = load_checkpoint(model, optimizer, path, map_location=args.device, ema=ema)
             print(f"[INFO] Loaded model and optimizer from checkpoint at epoch {initial_epoch} from {path}")
         criterion = YoloDFLQFLoss(num_classes=model_cfg["num_classes"], lambda_box=tr_cfg["weights"].get("bbox_loss", 1.5),
                                   lambda_cls=tr_cfg["weights"].get("cls_loss", 1.0))
@@ -103,7 +112,7 @@ def main(args):
               log_interval=tr_cfg.get("log_interval", 10), checkpoint_dir=ckpt_dir,
               iou_threshold=tr_cfg.get("iou_threshold", 0.5), conf_threshold=tr_cfg.get("conf_threshold", 0.25),
               distributed_mode=args.mode, precision=args.precision, captured_step=captured,
-              grad_compress=(tr_cfg.get("ddp") or {}).get("grad_compress"), max_grad_norm=max_grad_norm)
+              grad_compress=(tr_cfg.get("ddp") or {}).get("grad_compress"), max_grad_norm=max_grad_norm, ema=ema)
     finally:
         if run is not None:
             import wandb

@@ -21,6 +21,13 @@ src/training/train_model.py:247-253).
   deviation from clip_grad_norm_: the `.grad` tensors themselves are NOT modified.  (The reference's config.yaml carries
   training.grad_clip, but its loop never reads it.)  Not combined with DTensor parameters: the shard norms would need a
   collective.
+* `ema_decay=d` (with `ema_tau`): an exponential moving average of the weights -- the `ModelEMA` of the YOLOv5 / v8 recipes,
+  `ema = d_t*ema + (1-d_t)*w` after every step with `d_t = d*(1 - exp(-t/tau))` (tau 0: constant d) -- kept by the AdamW
+  kernel itself: one fp32 shadow per stepped parameter, no extra launch, inside a captured step.  `src/training/ema.py`
+  (`ModelEMA`) adds the BatchNorm running statistics, the swap for validation and the checkpoint form.  Deviations from the
+  host-side recipe: a step skipped on overflow moves neither the shadows nor t; a parameter without a gradient on a step is
+  not in the job table, so its shadow does not move on that step; the average is of the parameter AS STORED (a bf16
+  parameter's rounded value).  The reference has no EMA.  Not combined with DTensor parameters.
 There is no CPU path: parameters must live on the GPU (like every op of this package).
 """
 import torch
@@ -83,12 +90,19 @@ class DeviceGradScaler:
 class HipAdamW(torch.optim.Optimizer):
     _step_supports_amp_scaling = True      # GradScaler hands over grad_scale / found_inf instead of unscaling itself
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=True, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=True, max_grad_norm=None,
+                 ema_decay=None, ema_tau=2000.0):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid AdamW hyper-parameter")
         # an attribute of the optimizer, NOT a param_groups key and not in state_dict(): checkpoints stay loadable by
         # torch.optim.AdamW and the reference
         self.max_grad_norm = max_grad_norm
+        self._plans = {}                    # group index -> dict(ptrs, jobs_dev, njobs, nchunks, hyper, hyper_host, step, ema_ctl)
+        self._ema = {}                      # parameter -> fp32 shadow; on the optimizer but OUTSIDE self.state (checkpoints)
+        self._ema_buffers = None            # ModelEMA's job table over the model's float buffers (attach_ema_buffers)
+        self._ema_decay = None
+        self.ema_tau = ema_tau              # the same kind of attribute as max_grad_norm: validated, not in state_dict()
+        self.ema_decay = ema_decay
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                         foreach=None, capturable=True, differentiable=False, fused=True)
         super().__init__(params, defaults)
@@ -97,8 +111,8 @@ class HipAdamW(torch.optim.Optimizer):
             if max_grad_norm is not None:
                 raise ValueError("HipAdamW: max_grad_norm is not supported with DTensor (FSDP2) parameters: the global norm "
                                  "of sharded gradients needs a collective over the shard norms")
+        self._refuse_sharded_ema()
         self._clip = None                   # dict(state = fp32 [max_norm, total_norm, coef], host = uploaded max_norm, partials)
-        self._plans = {}                    # group index -> dict(ptrs, jobs_dev, njobs, nchunks, hyper, hyper_host, step)
         self._pending = []                  # (jobs_dev, pinned host table) awaiting upload after a capture
         # grad_scale / found_inf are NOT pre-defined: GradScaler.step multiplies an existing grad_scale attribute in,
         # sets both around step() and deletes them afterwards
@@ -146,15 +160,107 @@ class HipAdamW(torch.optim.Optimizer):
                                   partials=torch.zeros(nparts, dtype=torch.float32, device=dev))
         return c
 
+    # ------------------------------------------------------------------------------------------ weight EMA
+    @property
+    def ema_decay(self):
+        """Decay of the weight EMA kept inside the step, or None = no EMA.  A new value (and a new `ema_tau`) reaches the
+        device with the next `sync_hyper()`, so a captured step follows a decay schedule without recapture; switching
+        between None and a number after a capture raises, because the captured job tables differ."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        if value is not None:
+            value = float(value)
+            if not (0.0 < value < 1.0):                     # also rejects nan
+                raise ValueError(f"HipAdamW: ema_decay must lie strictly between 0 and 1, or be None (got {value})")
+        if (value is None) != (self._ema_decay is None):
+            if any(plan.get("cap_host") is not None for plan in self._plans.values()):
+                raise RuntimeError("HipAdamW: the EMA cannot be turned on or off after a graph capture (the captured job "
+                                   "tables carry the shadow pointers); capture again with a new optimizer")
+            for plan in self._plans.values():
+                plan["ptrs"] = None                         # the next step rebuilds the job table with / without shadows
+            if value is None:
+                # off: a later average starts afresh, at the weights of that time and with updates = 0, not from shadows
+                # that stopped following the weights when the average was switched off
+                self._ema.clear()
+                for plan in self._plans.values():
+                    plan["ema_ctl"][2:3].zero_()
+        self._ema_decay = value
+        if value is not None and hasattr(self, "param_groups"):
+            self._refuse_sharded_ema()
+
+    @property
+    def ema_tau(self):
+        """Ramp of the decay in updates: d_t = ema_decay * (1 - exp(-t / ema_tau)); 0 = constant decay."""
+        return self._ema_tau
+
+    @ema_tau.setter
+    def ema_tau(self, value):
+        value = float(value)
+        if not (0.0 <= value <= 1.7976931348623157e308):    # also rejects nan
+            raise ValueError(f"HipAdamW: ema_tau must be finite and >= 0 (got {value})")
+        self._ema_tau = value
+
+    def _refuse_sharded_ema(self):
+        if self._ema_decay is not None and any(isinstance(p, DTensor) for g in self.param_groups for p in g["params"]):
+            raise ValueError("HipAdamW: ema_decay is not supported with DTensor (FSDP2) parameters: every rank would average "
+                             "only its shard, and nothing gathers the shadows")
+
+    @property
+    def ema_updates(self):
+        """EMA updates so far (skipped steps do not count): a 0-dim float64 device view that later steps and replays
+        update in place, like `last_grad_norm`.  Reading it syncs the host: for logging and tests only."""
+        for gi in sorted(self._plans):
+            return self._plans[gi]["ema_ctl"][2]
+        raise RuntimeError("HipAdamW: no step has run yet and ema_prepare() was not called")
+
+    def ema_shadow(self, p):
+        """The fp32 shadow of parameter `p`, or None (EMA off, or `p` has never been stepped nor prepared)."""
+        return self._ema.get(p)
+
+    def _shadow(self, p):
+        e = self._ema.get(p)
+        if e is None:                                       # the EMA starts at the weights
+            if p.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HipAdamW: run one eager step before capturing a graph (the EMA shadows are created "
+                                   "there; a copy made while capturing would be replayed with every step)")
+            e = self._ema[p] = _loc(p).detach().clone().to(torch.float32).contiguous()
+        return e
+
+    def ema_prepare(self):
+        """Create the control blocks and the shadow of every trainable parameter NOW instead of on its first step, so
+        that `ModelEMA.load_state_dict` has something to copy into before the first step.  Needs `ema_decay`."""
+        if self._ema_decay is None:
+            raise RuntimeError("HipAdamW.ema_prepare: ema_decay is None")
+        for gi, group in enumerate(self.param_groups):
+            if group["params"]:
+                self._plan(group, gi)
+                for p in group["params"]:
+                    if p.requires_grad:
+                        self._shadow(p)
+
+    def attach_ema_buffers(self, table):
+        """`table` (ModelEMA's): dict(jobs_dev, njobs, nchunks) over tensors the optimizer does not step.  `step()` ends
+        with one launch over it -- after every group's AdamW launch, so the update count already includes the step."""
+        self._ema_buffers = table
+
     # ------------------------------------------------------------------------------------------ state
-    def _init_state(self, group, gi):
+    def _plan(self, group, gi):
         plan = self._plans.get(gi)
         if plan is None:
             dev = next(p.device for p in group["params"])
             plan = self._plans[gi] = dict(ptrs=None, jobs_dev=None, host=None, njobs=0, nchunks=0, hyper_host=None,
                                           hyper=torch.zeros(5, dtype=torch.float64, device=dev),
-                                          step=torch.zeros((), dtype=torch.float32, device=dev))
+                                          step=torch.zeros((), dtype=torch.float32, device=dev),
+                                          ema_ctl=torch.zeros(3, dtype=torch.float64, device=dev), ema_host=None)
+        return plan
+
+    def _init_state(self, group, gi):
+        plan = self._plan(group, gi)
         for p in group["params"]:
+            if self._ema_decay is not None and _grad(p) is not None:
+                self._shadow(p)
             st = self.state[p]
             if "exp_avg" not in st:
                 st["step"] = plan["step"]                           # one shared device counter per group
@@ -182,6 +288,10 @@ class HipAdamW(torch.optim.Optimizer):
             if plan["hyper_host"] != want:
                 plan["hyper"].copy_(torch.tensor(want, dtype=torch.float64))
                 plan["hyper_host"] = want
+            # decay and tau only: `updates` is the device's own count (ModelEMA.load_state_dict is its one other writer)
+            if self._ema_decay is not None and plan["ema_host"] != (self._ema_decay, self._ema_tau):
+                plan["ema_ctl"][0:2].copy_(torch.tensor([self._ema_decay, self._ema_tau], dtype=torch.float64))
+                plan["ema_host"] = (self._ema_decay, self._ema_tau)
         c = self._clip
         if c is not None and self._max_grad_norm is not None and c["host"] != self._max_grad_norm:
             c["state"][0:1].copy_(torch.tensor([self._max_grad_norm], dtype=torch.float32))
@@ -211,12 +321,14 @@ class HipAdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         """One launch for all parameters of a group.  Deviation from torch.optim.AdamW: the step counter (bias correction)
         is per GROUP, not per parameter -- a parameter that receives no gradient on some steps is corrected as if it had
-        been stepped with the others (the reference's model gives every parameter a gradient on every step)."""
+        been stepped with the others (the reference's model gives every parameter a gradient on every step).  The EMA
+        (`ema_decay`) shares that table: the update count is per group too, and a parameter without a gradient on a step
+        is not in the table, so its shadow does not move on that step."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        ready = []
+        ready, ema_ctl = [], None
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if _grad(p) is not None]
             if not params:
@@ -256,12 +368,24 @@ class HipAdamW(torch.optim.Optimizer):
                 self.sync_hyper()
             elif plan["hyper_host"] is None:
                 raise RuntimeError("HipAdamW: run one eager step (or sync_hyper()) before capturing a graph")
+            if ema_ctl is None:
+                ema_ctl, ema_on = plan["ema_ctl"], params[0]
             if self._max_grad_norm is not None:
                 ready.append((plan, params))        # clipped: the norm spans ALL groups, so the launches follow the loop
                 continue
             self._launch(plan, params)
         if ready:
             self._clipped_step(ready)
+        table = self._ema_buffers
+        if table is not None and self._ema_decay is not None and ema_ctl is not None:
+            # the statistics of a step that the scaler skipped stay out of the average too.  DeviceGradScaler's step has
+            # already handed found_inf on to last_found_inf (state[2]) and cleared it; GradScaler's attribute is still set.
+            # (DeviceGradScaler is for ONE parameter group: with several, unclipped, each group's launch decides and updates
+            # the scale on its own, as before the EMA existed, and state[2] is the LAST group's decision.)
+            amp = getattr(self, "device_amp", None)
+            skip = amp.state[2:3] if amp is not None else getattr(self, "found_inf", None)
+            lib.call("yolo_ema_lerp", _p(table["jobs_dev"]), table["njobs"], table["nchunks"], _p(ema_ctl), _p(skip),
+                     _stream(_loc(ema_on)))
         return loss
 
     def _launch(self, plan, params):
@@ -322,6 +446,11 @@ class HipAdamW(torch.optim.Optimizer):
             if not (g.numel() == m1.numel() == m2.numel() == w.numel()):
                 raise RuntimeError("HipAdamW: gradient / moment shards do not match the parameter's local shard")
             lib.call("yolo_adamw_job_fill", host.data_ptr(), i, _p(w), dt(w), _p(g), dt(g), _p(m1), _p(m2), w.numel())
+            if self._ema_decay is not None:
+                e = self._ema[p]
+                if e.numel() != w.numel() or e.device != w.device:
+                    raise RuntimeError("HipAdamW: an EMA shadow does not match its parameter's local shard")
+                lib.call("yolo_adamw_job_set_ema", host.data_ptr(), i, _p(e), _p(plan["ema_ctl"]))
         plan["nchunks"] = lib.query("yolo_adamw_jobs_finalize", host.data_ptr(), n)
         plan["njobs"] = n
         if capturing:

@@ -135,7 +135,10 @@ class ShardState:
         return dict(state=state, param_groups=[group])
 
 
-def _refuse_clipping(optimizer):
+def _refuse_unsupported(optimizer):
+    if getattr(optimizer, "ema_decay", None) is not None:
+        raise ValueError("ShardedStepRunner: ema_decay is not supported on the sharded route -- every rank would average only "
+                         "its shard of the master weights and nothing gathers the shadows; build the optimizer without it")
     if getattr(optimizer, "max_grad_norm", None) is not None:
         raise ValueError("ShardedStepRunner: max_grad_norm is not supported on the sharded route -- every rank steps only its "
                          "shard of the reduce-scattered gradient, so the global norm would need a collective over the shard "
@@ -149,7 +152,7 @@ class ShardedStepRunner(TrainStepRunner):
 
     def __init__(self, model, criterion, precision="bfloat16", lr=1e-3, weight_decay=1e-2, optimizer_factory=None, use_graph=True,
                  shard=None, optimizer=None):
-        _refuse_clipping(optimizer)
+        _refuse_unsupported(optimizer)
         sh = shard if shard is not None else ShardState(model, precision)
         if (shard is None) != (optimizer is None):
             raise ValueError("ShardedStepRunner: pass `shard` and the `optimizer` built over shard.master together")
@@ -168,7 +171,7 @@ class ShardedStepRunner(TrainStepRunner):
                 else:
                     optimizer_factory = lambda ps: torch.optim.AdamW(ps, lr=lr, weight_decay=weight_decay)
             optimizer = optimizer_factory([self.master])
-            _refuse_clipping(optimizer)
+            _refuse_unsupported(optimizer)
         super().__init__(model, criterion, optimizer, precision="float32", use_graph=use_graph)     # no autocast in FSDP modes
         self.comm, self.staged, self.buckets = False, False, None      # the exchange below replaces the DDP buckets
         # pack: every gradient into its slice of flat_g in one launch (the GradBuckets job table over OUR layout)

@@ -4,6 +4,8 @@
 Same step body as the reference -- zero_grad, autocast only in ddp mode, forward, loss, (scaled) backward,
 optimizer step -- on the HIP-backed model; host-side changes only: the three loss scalars arrive with one
 device->host copy per step (LazyLossDict) and the six per-epoch scalar all-reduces are two."""
+import contextlib
+
 import torch
 from torch.amp import GradScaler
 from tqdm import tqdm
@@ -77,10 +79,11 @@ class CapturedTraining:
     unscaled update and the scale's growth / backoff (GradScaler's rules and defaults, reference :195-208,247-253) run on the
     device inside the captured step (`DeviceGradScaler`, needs `HipAdamW`)."""
 
-    def __init__(self, model, criterion, optimizer, precision, grad_compress=None):
+    def __init__(self, model, criterion, optimizer, precision, grad_compress=None, ema=None):
         import torch.distributed as dist
         from torch.nn.parallel import DistributedDataParallel as DDP
         self.wrapper = model
+        self.ema = ema                      # ModelEMA or None: its buffer shadows are synchronised with the live buffers
         self.inner = model.module if isinstance(model, DDP) else model
         self.criterion, self.optimizer, self.precision = criterion, optimizer, precision
         if grad_compress not in (None, "", "none", "bf16", "bfloat16"):
@@ -146,9 +149,12 @@ class CapturedTraining:
 
     def sync_buffers(self):
         """DistributedDataParallel(broadcast_buffers=True) semantics for the BatchNorm buffers: rank 0's values on every
-        rank (one flat broadcast per dtype) -- call before evaluating or checkpointing."""
+        rank (one flat broadcast per dtype) -- call before evaluating or checkpointing.  The EMA's buffer shadows follow
+        the same rule."""
         if self.world == 1:
             return
+        if self.ema is not None:
+            self.ema.sync_buffers()
         import torch.distributed as dist
         by_dtype = {}
         for b in self.inner.buffers():
@@ -244,12 +250,23 @@ def _run_epoch(model, loader, criterion, device, autocast_kw, rank, desc, optimi
 def train(model, train_loader, val_loader, optimizer, scheduler, criterion, initial_epoch, num_epochs, device,
           num_classes=171, rank=0, use_wandb=False, wandb_instance=None, log_interval=10,
           checkpoint_dir="experiments/checkpoints", iou_threshold=0.5, conf_threshold=0.25, distributed_mode="ddp",
-          precision="float32", captured_step=None, grad_compress=None, max_grad_norm=None):
+          precision="float32", captured_step=None, grad_compress=None, max_grad_norm=None, ema=None):
     """`captured_step`: None (default) = the captured step where it applies AND has been verified on hardware (ddp mode on
     one GPU, plain parameters, capturable optimizer), True = also with more than one rank, False = the reference's eager
     loop.  `grad_compress`: None = fp32 gradient exchange (the reference's), "bf16" = bf16 buckets in the captured step.
     `max_grad_norm`: the config's optional training.max_grad_norm, as handed to get_optimizer (the clipping itself lives in
-    HipAdamW.step); here it only refuses the routes that cannot clip and enables the train/grad_norm log."""
+    HipAdamW.step); here it only refuses the routes that cannot clip and enables the train/grad_norm log.
+    `ema`: a `ModelEMA` (config key training.ema) or None.  The average itself is kept inside the optimizer step; here the
+    validation epoch -- loss, metrics and so the ReduceLROnPlateau schedule -- runs on the averaged weights
+    (`ema.applied(model)`), training continues on the raw ones, and the routes without an EMA are refused."""
+    if ema is not None:
+        if distributed_mode in ("fsdp", "fsdp2") or getattr(model, "_native_shard", None) is not None:
+            raise ValueError(f"training.ema is not supported in {distributed_mode} mode: the shadows of sharded parameters "
+                             "would be shards that nothing gathers; use ddp mode or remove the key")
+        from src.training.fused_adamw import HipAdamW
+        if not isinstance(optimizer, HipAdamW) or optimizer.ema_decay is None:
+            raise ValueError("training.ema is set but the optimizer keeps no average: it needs a HipAdamW with ema_decay set "
+                             "(build a ModelEMA over the optimizer that get_optimizer returns)")
     if max_grad_norm is None:
         max_grad_norm = getattr(optimizer, "max_grad_norm", None)
     if max_grad_norm is not None:
@@ -263,7 +280,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
     import torch.distributed as dist
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     want_captured = captured_step is True or (captured_step is None and world == 1)
-    captured = CapturedTraining(model, criterion, optimizer, precision, grad_compress=grad_compress) \
+    captured = CapturedTraining(model, criterion, optimizer, precision, grad_compress=grad_compress, ema=ema) \
         if (want_captured and device != "cpu" and distributed_mode == "ddp") else None
     if getattr(model, "_native_shard", None) is not None:       # fsdp2 with native_shard: the sharded step IS the training path
         captured = ShardedTraining(model, criterion, optimizer, precision)
@@ -300,10 +317,14 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
             tr = reduce_values(tr, average=True)
         if captured is not None:
             captured.sync_buffers()         # what DDP's per-forward buffer broadcast leaves: rank 0's running statistics
+        elif ema is not None:
+            # the eager loop under torch's DDP: the wrapper broadcasts the live buffers itself, before every forward; the
+            # averaged statistics are this rank's own until rank 0's are handed round here, before validation and checkpoint
+            ema.sync_buffers()
 
         model.eval()
         metrics.reset()
-        with torch.no_grad():
+        with torch.no_grad(), (ema.applied(model) if ema is not None else contextlib.nullcontext()):
             va = _run_epoch(model, val_loader, criterion, device, autocast_kw, rank,
                             f"[Epoch {epoch + 1}/{num_epochs}] Validation", metrics=metrics,
                             conf_threshold=conf_threshold, num_classes=num_classes)
@@ -320,7 +341,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
                                     "val/epoch_cls_loss": va[2], "val/precision": md["precision"],
                                     "val/recall": md["recall"], "val/f1_score": md["f1_score"], "val/mAP": md["mAP"],
                                     "lr": optimizer.param_groups[0]["lr"]})
-            save_checkpoint(model, optimizer, epoch + 1, va[0], checkpoint_dir=checkpoint_dir, states=states)
+            save_checkpoint(model, optimizer, epoch + 1, va[0], checkpoint_dir=checkpoint_dir, states=states, ema=ema)
             w = tqdm.write
             w("=" * 80)
             w(f"Epoch {epoch + 1}/{num_epochs} Summary:")

@@ -103,21 +103,31 @@ def checkpoint_states(model: nn.Module, optimizer: optim.Optimizer):
 
 
 def save_checkpoint(model: nn.Module, optimizer: optim.Optimizer, epoch: int, val_loss: float,
-                    checkpoint_dir: str = "experiments/checkpoints", states=None) -> None:
+                    checkpoint_dir: str = "experiments/checkpoints", states=None, ema=None) -> None:
     """{epoch, model_state, optimizer_state, val_loss} -> model_epoch_{E}.pth (reference :38-56).  `states`: the
-    result of checkpoint_states() when the model is sharded (gathered on all ranks before rank 0 calls this)."""
+    result of checkpoint_states() when the model is sharded (gathered on all ranks before rank 0 calls this).
+    `ema` (a ModelEMA): adds the top-level keys ema_state / ema_updates / ema_decay / ema_tau; model_state stays the raw
+    weights, which a resumed run needs."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = f"{checkpoint_dir}/model_epoch_{epoch}.pth"
     model_state, opt_state = states if states is not None else checkpoint_states(model, optimizer)
-    torch.save({"epoch": epoch, "model_state": model_state, "optimizer_state": opt_state, "val_loss": val_loss}, path)
+    ck = {"epoch": epoch, "model_state": model_state, "optimizer_state": opt_state, "val_loss": val_loss}
+    if ema is not None:
+        sd = ema.state_dict()
+        ck.update(ema_state=sd["ema_state"], ema_updates=sd["updates"], ema_decay=sd["decay"], ema_tau=sd["tau"])
+    torch.save(ck, path)
     print(f"[INFO] Saved checkpoint at {path}")
 
 
-def load_checkpoint(model: nn.Module, optimizer: optim.Optimizer, path: str, map_location="cpu") -> int:
+def load_checkpoint(model: nn.Module, optimizer: optim.Optimizer, path: str, map_location="cpu", ema=None) -> int:
     """Resume from a checkpoint written by this package or by the reference, under any wrapper: returns the epoch.
     Model keys are matched by canonical name; sharded models take full tensors through torch.distributed.checkpoint
-    (collective).  The optimizer state is loaded when given and present."""
+    (collective).  The optimizer state is loaded when given and present.  `ema` (a ModelEMA over plain parameters): restored
+    from the checkpoint's ema_* keys; a checkpoint without them (an older one, the reference's) restarts the average at the
+    loaded weights with updates = 0."""
     ck = torch.load(path, map_location=map_location, weights_only=False)
+    if ema is not None and (getattr(model, "_native_shard", None) is not None or _is_sharded(model)):
+        raise ValueError("load_checkpoint: ema is not supported for sharded models")
     state = canonical_state_dict(ck["model_state"] if isinstance(ck, dict) and "model_state" in ck else ck)
     native = getattr(model, "_native_shard", None)
     if native is not None:
@@ -169,6 +179,13 @@ def load_checkpoint(model: nn.Module, optimizer: optim.Optimizer, path: str, map
         target.load_state_dict(state)
         if optimizer is not None and isinstance(ck, dict) and "optimizer_state" in ck:
             optimizer.load_state_dict(ck["optimizer_state"])
+        if ema is not None:
+            if isinstance(ck, dict) and "ema_state" in ck:
+                ema.load_state_dict(dict(ema_state=ck["ema_state"], updates=ck["ema_updates"], decay=ck["ema_decay"],
+                                         tau=ck["ema_tau"]))
+            else:
+                ema.reset_from_model()
+                print(f"[INFO] {path} carries no EMA: the average restarts at the loaded weights (updates = 0)")
     return int(ck["epoch"]) if isinstance(ck, dict) and "epoch" in ck else 0
 
 

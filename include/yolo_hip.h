@@ -77,6 +77,17 @@ int yolo_adamw_job_fill(void* jobs_host, int index, void* p, int p_dtype, const 
 long yolo_adamw_jobs_finalize(void* jobs_host, int njobs);
 int yolo_adamw_jobs_set_grads(void* jobs_host, int njobs, const void* const* grads);
 int yolo_adamw_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale, const float* found_inf, hipStream_t st);
+/* exponential moving average of the weights (the ModelEMA of the YOLOv5 / v8 recipes; the reference has NO EMA: its step,
+   train_model.py:247-253, is followed by nothing that averages, and it validates and saves the raw weights).
+   yolo_adamw_job_set_ema gives record `index` an fp32 shadow and the control block of its parameter group, ema_ctl = device
+   doubles [decay, tau, updates] (null / null = no EMA; yolo_adamw_job_fill clears both).  Every step entry point of this
+   block then also leaves ema = d*ema + (1-d)*w behind, w = the parameter as stored, d = tau > 0 ? decay*(1 - exp(-updates/tau))
+   : decay, and counts `updates` with `step`; a step skipped on found_inf moves neither.  yolo_ema_lerp is the same average
+   for tensors the optimizer does not step (BatchNorm running statistics): a table of records with p (read) and the shadow,
+   g / m / v null, launched AFTER the step's AdamW launches; it does nothing when skip_flag is given and non-zero (under
+   yolo_adamw_amp_step that flag is amp_state[2], because the step's closing scale update clears amp_state[1]). */
+int yolo_adamw_job_set_ema(void* jobs_host, int index, float* ema, double* ema_ctl);
+int yolo_ema_lerp(const void* jobs_dev, int njobs, long nchunks, const double* ema_ctl, const float* skip_flag, hipStream_t st);
 /* fp16 dynamic loss scaling without the host (GradScaler's scale / step / update, train_model.py:195-208,247-253): amp_state = fp32 [scale, found_inf (0 on entry), last_found_inf]; the gradients carry the factor `scale` (see yolo_loss_dfl_qfl's grad_scale) */
 int yolo_adamw_amp_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, float* amp_state, int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, hipStream_t st);
 /* global-norm gradient clipping on the device (torch.nn.utils.clip_grad_norm_, norm_type 2, then the AdamW step; the reference's
