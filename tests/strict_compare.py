@@ -50,7 +50,7 @@ C_DEFAULT = 16.0
 C = {f: C_DEFAULT for f in ("gather", "ring", "rows", "halo", "patch", "auto", "generic", "fp32", "stem", "depthwise",
                             "wgrad", "wgrad_atomics", "auto_wgrad", "generic_wgrad", "fp32_wgrad", "stem_wgrad", "depthwise_wgrad")}
 OBSERVED = {}          # family -> [max excess in units of 2^-24 M, elements compared, cases]
-BUDGET_FAMILIES = set()   # families whose M is a whole noise budget / 2^-24 (strict_attention.py): the figure is a share, limit 1
+BUDGET_FAMILIES = set()   # families whose M is a whole noise budget / 2^-24 (strict_attention.py, strict_bn.py): the figure is a share, limit 1
 
 
 class StrictMismatch(AssertionError):
@@ -226,7 +226,7 @@ def report():
         lines.append(f"[strict_compare]   {fam:16s} {ex:8.3f}   (c = {C.get(fam, C_DEFAULT):g}; {cases} comparisons, {elems} elements)")
     att = sorted(f for f in OBSERVED if f in BUDGET_FAMILIES)
     if att:
-        lines.append("[strict_compare] attention: max of (|got - ref| - 1/2 ulp) / noise budget per family (limit 1):")
+        lines.append("[strict_compare] attention, BatchNorm: max of (|got - ref| - 1/2 ulp) / noise budget per family (limit 1):")
         for fam in att:
             ex, elems, cases = OBSERVED[fam]
             lines.append(f"[strict_compare]   {fam:16s} {ex:8.3f}   (c = {C.get(fam, C_DEFAULT):g}; {cases} comparisons, {elems} elements)")

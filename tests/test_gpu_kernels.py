@@ -2,7 +2,8 @@
 
 The convolution family (dense, stem, depthwise; forward, data and weight gradients, fused inference epilogues) is held to
 the derived per-element bound of tests/strict_compare.py against a float64 reference, attention (every route, its stash
-and its three gradients) to that of tests/strict_attention.py.  The other leaves keep check():
+and its three gradients) to that of tests/strict_attention.py; the BatchNorm leaves are held to tests/strict_bn.py in
+tests/test_gpu_bn.py, and their check() cases here stay as the end-to-end anchor.  The other leaves keep check():
 tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
 and round once, the stand-in does the same from the same rounded inputs, so 2 output ulps
 (bf16: 2^-7, f16: 2^-10 relative) of the tensor's max magnitude.  Integer outputs (pool argmax,
