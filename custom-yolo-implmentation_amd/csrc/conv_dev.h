@@ -1,7 +1,10 @@
-// Device-side pieces shared by the conv kernels (conv_mfma.hip, conv_halo.hip): MFMA wrappers, the packed
-// geometry passed by value, the XCD-aware tile order and the 16-lane row reduction.
+// Device-side pieces shared by the MFMA conv kernels (conv_mfma / conv_ring / conv_rows / conv_halo / conv_up2.hip and the
+// fused stem of stem.hip): MFMA wrappers, the packed geometry passed by value, the XCD-aware tile order, and the ONE copy of
+// the kernels' tail -- bias gather, linear pixel walk, pixel store (ConvEpi, store_pixel_blocks) and the BatchNorm
+// statistics epilogue (conv_stats_epilogue) -- plus the accumulate dispatch of their launchers (with_acc).
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 #include "conv_host.h"
 
 namespace {
@@ -30,18 +33,23 @@ constexpr int LDSROW = 32; // elements per LDS row: unpadded 64-byte rows whose 
                            // by (-(row >> 2)) & 3 -- conflict-free for ds_read_b128 fragment reads (16 rows x 1 chunk
                            // per lane group) and for the ds_write_b128 staging (2 rows x 4 chunks per 8 lanes)
 
+// What the kernels' shared tail reads, declared once and embedded in every family's kernarg struct (to_epi fills it)
+struct ConvEpi {
+    int Cd, ldd;                 // destination channels and row stride
+    int act;                     // inference epilogue: 1 = SiLU after the bias
+    int ldr, ld2;                // row strides of res / acc2
+    int wide;                    // 16-byte epilogue stores where the destination allows (YOLO_CONV_WIDE=0: the 8-byte form, A/B runs)
+    const void* res;             // inference epilogue: residual added after the activation (row stride ldr) or null
+    const void* acc2;            // ACC launches: second accumulate source (row stride ld2) or null
+    float* stats;                // optional [8][2][Cd] batch-statistics accumulator (forward of a BN conv)
+};
+
 struct GeomDev {           // ConvGeom with the tap offsets packed (no dynamic indexing of kernargs)
-    int N, Hs, Ws, Cs, lds, Hd, Wd, Cd, ldd, Hg, Wg, ostep, ooff_h, ooff_w, sstride, ntaps, KT, Kpad;
+    int N, Hs, Ws, Cs, lds, Hd, Wd, Hg, Wg, ostep, ooff_h, ooff_w, sstride, ntaps, KT, Kpad;
     unsigned dh_pack, dw_pack;   // 2 bits per tap: value + 1
     int tap_inner;               // MODE 2 K order: 1 = taps innermost, 0 = channel chunks innermost
     int dma;                     // MODE 2 -> 3: tiles go global -> LDS by LDS-DMA instead of through registers
-    float* stats;                // optional [8][2][Cd] batch-statistics accumulator (forward of a BN conv)
-    const void* acc2;            // ACC launches: second accumulate source (row stride ld2) or null
-    int ld2;
-    int wide;                    // 16-byte epilogue stores where the destination allows (YOLO_CONV_WIDE=0: the 8-byte form, A/B runs)
-    int act;                     // inference epilogue: 1 = SiLU after the bias
-    const void* res;             // inference epilogue: residual added after the activation (row stride ldr) or null
-    int ldr;
+    ConvEpi e;
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -97,14 +105,14 @@ __device__ __forceinline__ unsigned swap_rows16(unsigned v, bool odd_row) {
 
 // Epilogue of one output pixel: the WN 16-channel blocks of accumulator row `a` (lane: channels cq .. cq+3 of every block,
 // pixel = the lane's fr) -> bias, inference act / residual, accumulate sources, store.  Shared by the five MFMA conv kernels.
-// 16-byte stores where the destination allows it (base 16-byte aligned, row stride a multiple of 8 channels, G::wide): lanes
+// 16-byte stores where the destination allows it (base 16-byte aligned, row stride a multiple of 8 channels, ConvEpi::wide): lanes
 // (fr, fg) and (fr, fg ^ 1) hold neighbouring channel quads of the SAME pixel for every block j; one dword pair swapped
 // between them (lane ^ 16) leaves the even lane with 8 consecutive channels of block j and the odd lane with 8 of block j+1 --
 // half as many, twice as wide write requests per wave instruction (same-box A/B on the step with k_conv_mfma alone:
 // 10.51 -> 10.38 ms; 512 -> 128 @80x80 data gradient 97 -> 78 us).  EVERY lane of the wave must call this (`live` false
 // for pixels outside the map): the exchange is a cross-lane operation.
-template <typename T, int WN, bool ACC, typename G>
-__device__ __forceinline__ void store_pixel_blocks(const G& g, const f32x4 (&a)[WN], const float (&bv)[WN][4], T* __restrict__ dst,
+template <typename T, int WN, bool ACC>
+__device__ __forceinline__ void store_pixel_blocks(const ConvEpi& g, const f32x4 (&a)[WN], const float (&bv)[WN][4], T* __restrict__ dst,
                                                    long pix, bool live, int cbase, int cq, int lane) {
     T* drow = dst + pix * g.ldd;
     auto values = [&](int j, float (&v)[4]) {
@@ -163,20 +171,134 @@ __device__ __forceinline__ void store_pixel_blocks(const G& g, const f32x4 (&a)[
     }
 }
 
+// bias of the lane's four channels in each of its WN 16-channel blocks (channels cbase + j*16 + cq ..+3); 0 without a bias
+// and past the last channel.  Cd is read from the record HERE, not passed by value: handed in as a value it is loaded at the
+// call and k_conv_halo, k_conv_ring and the accumulating k_conv_mfma allocate 1-12 more VGPRs (one halo tile loses a wave).
+template <int WN>
+__device__ __forceinline__ void bias_blocks(const float* __restrict__ bias, int cbase, int cq, const ConvEpi& e, float (&bv)[WN][4]) {
+#pragma unroll
+    for (int j = 0; j < WN; ++j) {
+        const int c = cbase + j * 16 + cq;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bv[j][r] = (bias != nullptr && c < e.Cd) ? bias[c + r] : 0.f;
+    }
+}
+
+// Epilogue walk of the kernels whose tile is a run of the linear pixel index of an Hg x Wg grid: the first pixel's
+// coordinates come from two divisions, the following ones (+16 pixels each) by carrying.
+struct LinearPixels {
+    int q, npix, Wg, Hg, n, a, b;
+    __device__ __forceinline__ void start(int q0, int npix_, int Wg_, int Hg_) {
+        q = q0; npix = npix_; Wg = Wg_; Hg = Hg_;
+        const unsigned qq = q < npix ? q : 0;
+        const unsigned t2 = qq / (unsigned)Wg;
+        b = (int)(qq - t2 * Wg);
+        n = (int)(t2 / (unsigned)Hg);
+        a = (int)t2 - n * Hg;
+    }
+    __device__ __forceinline__ bool live() const { return q < npix; }
+    // destination pixel index of grid pixel (n, a, b); 0 for a dead pixel
+    __device__ __forceinline__ long pix(int Hd, int Wd, int ostep, int ooff_h, int ooff_w) const {
+        return live() ? ((long)n * Hd + a * ostep + ooff_h) * (long)Wd + b * ostep + ooff_w : 0;
+    }
+    __device__ __forceinline__ void advance16() {
+        q += 16;
+        b += 16;
+        while (b >= Wg) {
+            b -= Wg;
+            if (++a == Hg) { a = 0; ++n; }
+        }
+    }
+};
+
+// ---- BatchNorm batch statistics of the values just stored: per-channel sum / sum of squares, no second pass over y.
+// sacc = [2][BN] floats of LDS.
+__device__ __forceinline__ void stats_zero(float* sacc, int n, int tid, int nthr) {
+    for (int t = tid; t < n; t += nthr) sacc[t] = 0.f;
+}
+// the lane's accumulators rounded to T (the stored values), summed over its WM pixels and then over the 16 pixels of the
+// lane row; the fr == 0 lanes add the row's sums to sacc
+template <typename T, int WM, int WN>
+__device__ __forceinline__ void stats_lane_sums(const f32x4 (&acc)[WM][WN], float* sacc, int BN, int crow, int cq, int fr) {
+#pragma unroll
+    for (int j = 0; j < WN; ++j) {
+        float s[4] = {0.f, 0.f, 0.f, 0.f}, q2[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float v = to_f<T>(from_f<T>(acc[i][j][r]));
+                s[r] += v;
+                q2[r] += v * v;
+            }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s[r] = row16_sum(s[r]);
+            q2[r] = row16_sum(q2[r]);
+        }
+        if (fr == 0) {
+            const int cl = crow + j * 16 + cq;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                atomicAdd(&sacc[cl + r], s[r]);
+                atomicAdd(&sacc[BN + cl + r], q2[r]);
+            }
+        }
+    }
+}
+// the workgroup's sums -> replica (workgroup mod 8) of stats[8][2][Cd]
+__device__ __forceinline__ void stats_flush(const float* sacc, int BN, float* stats, int cd0, int Cd, int tid, int nthr) {
+    float* o = stats + (long)(blockIdx.x & 7) * 2 * Cd;
+    for (int t = tid; t < BN; t += nthr)
+        if (cd0 + t < Cd) {
+            atomicAdd(o + cd0 + t, sacc[t]);
+            atomicAdd(o + Cd + cd0 + t, sacc[BN + t]);
+        }
+}
+// The statistics epilogue of a conv kernel whose workgroup (nthr threads) owns channels cd0 .. cd0+BN-1; acc[i][j] = the
+// lane's pixel tile i, 16-channel block j (channels crow + j*16 + cq ..+3 of the tile).  The contract:
+//   * ALL threads of the workgroup call it (two barriers inside);
+//   * LDS is idle at the call: sacc may alias what the K loop used, so every wave is past its last LDS read and no LDS-DMA
+//     is in flight (the caller's barrier, where its K loop does not end in one);
+//   * acc rows of dead pixels (outside the map, past the last pixel) hold 0;
+//   * acc is the raw conv result: no bias (a launch has a bias or statistics, not both), rounded here as the store rounds it;
+//   * the sums are ADDED to replica blockIdx.x & 7 of stats[8][2][Cd]: the consumer sums all eight.
+template <typename T, int WM, int WN>
+__device__ __forceinline__ void conv_stats_epilogue(const f32x4 (&acc)[WM][WN], float* sacc, int BN, float* stats, int cd0, int Cd,
+                                                    int crow, int cq, int fr, int tid, int nthr) {
+    stats_zero(sacc, 2 * BN, tid, nthr);
+    __syncthreads();
+    stats_lane_sums<T, WM, WN>(acc, sacc, BN, crow, cq, fr);
+    __syncthreads();
+    stats_flush(sacc, BN, stats, cd0, Cd, tid, nthr);
+}
+
+// ---- host side
+inline ConvEpi to_epi(const ConvGeom& g) {
+    ConvEpi e;
+    e.Cd = g.Cd; e.ldd = g.ldd; e.act = g.act; e.ldr = g.ldr; e.ld2 = g.ld2;
+    e.wide = conv_wide_flag();
+    e.res = g.res; e.acc2 = g.acc2; e.stats = g.stats;
+    return e;
+}
+
 inline GeomDev to_dev(const ConvGeom& g) {
     GeomDev d;
-    d.N = g.N; d.Hs = g.Hs; d.Ws = g.Ws; d.Cs = g.Cs; d.lds = g.lds; d.Hd = g.Hd; d.Wd = g.Wd; d.Cd = g.Cd;
-    d.ldd = g.ldd; d.Hg = g.Hg; d.Wg = g.Wg; d.ostep = g.ostep; d.ooff_h = g.ooff_h; d.ooff_w = g.ooff_w;
+    d.N = g.N; d.Hs = g.Hs; d.Ws = g.Ws; d.Cs = g.Cs; d.lds = g.lds; d.Hd = g.Hd; d.Wd = g.Wd;
+    d.Hg = g.Hg; d.Wg = g.Wg; d.ostep = g.ostep; d.ooff_h = g.ooff_h; d.ooff_w = g.ooff_w;
     d.sstride = g.sstride; d.ntaps = g.ntaps; d.Kpad = g.Kpad; d.KT = g.Kpad / BK;
     pack_taps(g, &d.dh_pack, &d.dw_pack);
-    d.stats = g.stats;
-    d.acc2 = g.acc2; d.ld2 = g.ld2;
-    d.act = g.act; d.res = g.res; d.ldr = g.ldr;
-    d.wide = conv_wide_flag();
     d.tap_inner = 0;
     d.dma = 1;      // LDS-DMA staging: level or a few % ahead of register staging on every shape of tools/conv_tune.py
+    d.e = to_epi(g);
     return d;
 }
 
+// f(std::true_type / std::false_type): the ACC template argument of a kernel from the launch's run-time flag
+template <typename F>
+decltype(auto) with_acc(int accumulate, F&& f) {
+    if (accumulate) return f(std::bool_constant<true>{});
+    return f(std::bool_constant<false>{});
+}
 
 }  // namespace

@@ -43,7 +43,7 @@ __global__ __launch_bounds__((TH / 4) * (BN / 64) * 64) void k_conv_halo(GeomDev
     const int shift = (g.Ws + 1) * g.lds;
     const __amdgpu_buffer_rsrc_t rsa =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, (g.N * g.Hs * g.Ws * g.lds + shift) * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.Cd * g.Kpad * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.e.Cd * g.Kpad * 2, 0x00020000);
     int hvoff[HR], hlds[HR];
 #pragma unroll
     for (int r = 0; r < HR; ++r) {
@@ -62,7 +62,7 @@ __global__ __launch_bounds__((TH / 4) * (BN / 64) * 64) void k_conv_halo(GeomDev
 #pragma unroll
     for (int i = 0; i < WR; ++i) {
         const int row = wrow0 + i * (NTHR / 4);
-        wvoff[i] = (cd0 + row < g.Cd) ? ((cd0 + row) * g.Kpad + kseg * 8) * 2 : (int)0x80000000;
+        wvoff[i] = (cd0 + row < g.e.Cd) ? ((cd0 + row) * g.Kpad + kseg * 8) * 2 : (int)0x80000000;
     }
 
     uint4 rh[HR], rw[WR];
@@ -141,18 +141,13 @@ __global__ __launch_bounds__((TH / 4) * (BN / 64) * 64) void k_conv_halo(GeomDev
     // ---- epilogue: lane holds channels c..c+3 of pixel (row wgm*4+i, col fr)
     const int cq = fg * 4;
     float bv[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = cd0 + crow + j * 16 + cq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bv[j][r] = (bias != nullptr && c < g.Cd) ? bias[c + r] : 0.f;
-    }
+    bias_blocks<4>(bias, cd0 + crow, cq, g.e, bv);
     const int ox = x0 + fr;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int oy = y0 + wgm * 4 + i;
         const bool pv = oy < g.Hg && ox < g.Wg;
-        store_pixel_blocks<T, 4, ACC>(g, acc[i], bv, dst, pv ? ((long)n * g.Hd + oy) * (long)g.Wd + ox : 0, pv, cd0 + crow, cq, lane);
+        store_pixel_blocks<T, 4, ACC>(g.e, acc[i], bv, dst, pv ? ((long)n * g.Hd + oy) * (long)g.Wd + ox : 0, pv, cd0 + crow, cq, lane);
         if (!pv) {
             // pixels outside the map must not reach the statistics
 #pragma unroll
@@ -160,59 +155,21 @@ __global__ __launch_bounds__((TH / 4) * (BN / 64) * 64) void k_conv_halo(GeomDev
         }
     }
 
-    // ---- optional BatchNorm batch statistics of the stored (rounded) values, as in k_conv_mfma
-    float* const stats = g.stats;
-    if (stats != nullptr) {
-        float* sacc = reinterpret_cast<float*>(&wl[0][0][0]);             // [2][BN]; LDS is idle after the K loop
-        for (int t = tid; t < 2 * BN; t += NTHR) sacc[t] = 0.f;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float s[4] = {0.f, 0.f, 0.f, 0.f}, q2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = to_f<T>(from_f<T>(acc[i][j][r]));
-                    s[r] += v;
-                    q2[r] += v * v;
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[r] = row16_sum(s[r]);
-                q2[r] = row16_sum(q2[r]);
-            }
-            if (fr == 0) {
-                const int cl = crow + j * 16 + cq;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    atomicAdd(&sacc[cl + r], s[r]);
-                    atomicAdd(&sacc[BN + cl + r], q2[r]);
-                }
-            }
-        }
-        __syncthreads();
-        float* o = stats + (long)(blockIdx.x & 7) * 2 * g.Cd;
-        for (int t = tid; t < BN; t += NTHR)
-            if (cd0 + t < g.Cd) {
-                atomicAdd(o + cd0 + t, sacc[t]);
-                atomicAdd(o + g.Cd + cd0 + t, sacc[BN + t]);
-            }
-    }
+    // ---- optional BatchNorm batch statistics (LDS is idle after the K loop's last barrier)
+    if (g.e.stats != nullptr)
+        conv_stats_epilogue<T, 4, 4>(acc, reinterpret_cast<float*>(&wl[0][0][0]), BN, g.e.stats, cd0, g.e.Cd, crow, cq, fr, tid, NTHR);
 }
 
 template <typename T, int TH, int BN>
 void launch_halo(const GeomDev& d, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
                  hipStream_t st) {
     constexpr int NTHR = (TH / 4) * (BN / 64) * 64;
-    const int th = (d.Hg + TH - 1) / TH, tw = (d.Wg + 15) / 16, tn = (d.Cd + BN - 1) / BN;
+    const int th = (d.Hg + TH - 1) / TH, tw = (d.Wg + 15) / 16, tn = (d.e.Cd + BN - 1) / BN;
     const dim3 grid((unsigned)(d.N * th * tw * tn));
-    if (accumulate)
-        hipLaunchKernelGGL((k_conv_halo<T, TH, BN, true>), grid, dim3(NTHR), 0, st, d, (const T*)src, (const T*)wm, bias,
-                           (T*)dst, th, tw, tn);
-    else
-        hipLaunchKernelGGL((k_conv_halo<T, TH, BN, false>), grid, dim3(NTHR), 0, st, d, (const T*)src, (const T*)wm, bias,
-                           (T*)dst, th, tw, tn);
+    with_acc(accumulate, [&](auto acc) {
+        hipLaunchKernelGGL((k_conv_halo<T, TH, BN, decltype(acc)::value>), grid, dim3(NTHR), 0, st, d, (const T*)src, (const T*)wm,
+                           bias, (T*)dst, th, tw, tn);
+    });
 }
 
 }  // namespace

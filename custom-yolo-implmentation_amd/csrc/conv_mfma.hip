@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
     for (int i = 0; i < WR; ++i) {
         const int r = lrow + i * 64;
-        wvalid[i] = (r < BN) && (cd0 + r < g.Cd);
+        wvalid[i] = (r < BN) && (cd0 + r < g.e.Cd);
     }
 
     uint4 ra[2], rb[WR];
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const int shift = (g.Ws + 1) * g.lds;
         rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, (g.N * g.Hs * g.Ws * g.lds + shift) * 2,
                                                 0x00020000);
-        rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.Cd * g.Kpad * 2, 0x00020000);
+        rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.e.Cd * g.Kpad * 2, 0x00020000);
         // register staging: this thread loads chunk kseg and stores it at the swizzled slot; LDS-DMA: the lane's
         // slot is fixed (lane-linear image), so it loads the chunk that belongs there
         const int kload = MODE == 3 ? (kseg ^ ((-(lrow >> 2)) & 3)) : kseg;
@@ -236,77 +236,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         }
     }
 
-    // ---- epilogue: lane holds channels cbase..cbase+3 of pixel (tile pixel i*16 + fr).  The first pixel's
-    // coordinates come from two divisions, the following ones (+16 pixels each) by carrying.
+    // ---- epilogue: lane holds channels cbase..cbase+3 of pixel (tile pixel i*16 + fr)
     const int cq = (lane >> 4) * 4;
     float bv[WN][4];
+    bias_blocks<WN>(bias, cd0 + crow, cq, g.e, bv);
+    LinearPixels px;
+    px.start(m0 + prow + fr, total_pix, g.Wg, g.Hg);
 #pragma unroll
-    for (int j = 0; j < WN; ++j) {
-        const int c = cd0 + crow + j * 16 + cq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bv[j][r] = (bias != nullptr && c < g.Cd) ? bias[c + r] : 0.f;
-    }
-    {
-        int q = m0 + prow + fr;
-        const unsigned qq = q < total_pix ? q : 0;
-        const unsigned t2 = qq / (unsigned)g.Wg;
-        int b = (int)(qq - t2 * g.Wg);
-        int n = (int)(t2 / (unsigned)g.Hg);
-        int a = (int)t2 - n * g.Hg;
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-            const bool live = q < total_pix;
-            const long pix = live ? ((long)n * g.Hd + a * g.ostep + g.ooff_h) * (long)g.Wd + b * g.ostep + g.ooff_w : 0;
-            store_pixel_blocks<T, WN, ACC>(g, acc[i], bv, dst, pix, live, cd0 + crow, cq, lane);
-            q += 16;
-            b += 16;
-            while (b >= g.Wg) {
-                b -= g.Wg;
-                if (++a == g.Hg) { a = 0; ++n; }
-            }
-        }
+    for (int i = 0; i < WM; ++i) {
+        store_pixel_blocks<T, WN, ACC>(g.e, acc[i], bv, dst, px.pix(g.Hd, g.Wd, g.ostep, g.ooff_h, g.ooff_w), px.live(), cd0 + crow, cq, lane);
+        px.advance16();
     }
 
-    // ---- optional: per-channel sum / sum of squares of the values just stored (rounded to T), added to
-    // replica (workgroup mod 8) of stats[8][2][Cd]: BatchNorm batch statistics without a second pass over y
-    float* const stats = g.stats;
-    if (stats != nullptr) {
-        float* sacc = reinterpret_cast<float*>(&lds_a[0][0][0]);          // [2][BN]; LDS is idle after the K loop
-        for (int t = tid; t < 2 * BN; t += 256) sacc[t] = 0.f;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            float s[4] = {0.f, 0.f, 0.f, 0.f}, q2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = to_f<T>(from_f<T>(acc[i][j][r]));     // rows past the last pixel hold 0
-                    s[r] += v;
-                    q2[r] += v * v;
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[r] = row16_sum(s[r]);
-                q2[r] = row16_sum(q2[r]);
-            }
-            if (fr == 0) {
-                const int cl = crow + j * 16 + cq;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    atomicAdd(&sacc[cl + r], s[r]);
-                    atomicAdd(&sacc[BN + cl + r], q2[r]);
-                }
-            }
-        }
-        __syncthreads();
-        float* o = stats + (long)(blockIdx.x & 7) * 2 * g.Cd;
-        for (int t = tid; t < BN; t += 256)
-            if (cd0 + t < g.Cd) {
-                atomicAdd(o + cd0 + t, sacc[t]);
-                atomicAdd(o + g.Cd + cd0 + t, sacc[BN + t]);
-            }
-    }
+    // ---- optional BatchNorm batch statistics (rows past the last pixel hold 0; LDS is idle after the K loop's last barrier)
+    if (g.e.stats != nullptr)
+        conv_stats_epilogue<T, WM, WN>(acc, reinterpret_cast<float*>(&lds_a[0][0][0]), BN, g.e.stats, cd0, g.e.Cd, crow, cq, fr, tid, 256);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -410,16 +354,17 @@ void launch_tile(const GeomDev& d, const void* src, const void* wm, const float*
                  hipStream_t st) {
     constexpr int BN = WGN * WN * 16;
     long pix = (long)d.N * d.Hg * d.Wg;
-    int tm = (int)((pix + BM - 1) / BM), tn = (d.Cd + BN - 1) / BN;
+    int tm = (int)((pix + BM - 1) / BM), tn = (d.e.Cd + BN - 1) / BN;
     dim3 grid(tm * tn);
     int mode = d.Cs < BK ? 1 : (d.Cs % BK == 0 ? 2 : 0);
     if (mode == 2 && d.dma) mode = 3;
-#define CONV_LAUNCH(ACC_, SM_)                                                                                        \
-    hipLaunchKernelGGL((k_conv_mfma<T, WGM, WGN, WM, WN, ACC_, SM_>), grid, dim3(256), 0, st, d, (const T*)src,       \
-                       (const T*)wm, bias, (T*)dst, tn)
-    if (accumulate) { if (mode == 1) CONV_LAUNCH(true, 1); else if (mode == 2) CONV_LAUNCH(true, 2); else if (mode == 3) CONV_LAUNCH(true, 3); else CONV_LAUNCH(true, 0); }
-    else { if (mode == 1) CONV_LAUNCH(false, 1); else if (mode == 2) CONV_LAUNCH(false, 2); else if (mode == 3) CONV_LAUNCH(false, 3); else CONV_LAUNCH(false, 0); }
+    with_acc(accumulate, [&](auto acc) {
+#define CONV_LAUNCH(SM_)                                                                                              \
+    hipLaunchKernelGGL((k_conv_mfma<T, WGM, WGN, WM, WN, decltype(acc)::value, SM_>), grid, dim3(256), 0, st, d,      \
+                       (const T*)src, (const T*)wm, bias, (T*)dst, tn)
+        if (mode == 1) CONV_LAUNCH(1); else if (mode == 2) CONV_LAUNCH(2); else if (mode == 3) CONV_LAUNCH(3); else CONV_LAUNCH(0);
 #undef CONV_LAUNCH
+    });
 }
 
 template <typename T>

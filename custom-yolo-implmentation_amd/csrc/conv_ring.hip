@@ -27,14 +27,8 @@ struct RingSub {
     unsigned dh_pack, dw_pack;
 };
 struct RingGeom {
-    int N, Hs, Ws, Cs, lds, Hd, Wd, Cd, ldd, ostep, sstride, nsub, spt, ntile_n, wm_elems;
-    float* stats;
-    const void* acc2;           // ACC launches: second accumulate source (row stride ld2) or null
-    int ld2;
-    int wide;                   // 16-byte epilogue stores (see store_pixel_blocks)
-    int act;                    // inference epilogue (see ConvGeom)
-    const void* res;
-    int ldr;
+    int N, Hs, Ws, Cs, lds, Hd, Wd, ostep, sstride, nsub, spt, ntile_n, wm_elems;
+    ConvEpi e;
     RingSub sub[4];
 };
 
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
     for (int j = 0; j < LB; ++j) {
         const int row = wave * (BN / 4) + j * RPP + rp;
         const int chunk = slot ^ ring_swz<RB>(row);
-        voffb[j] = (cd0 + row < g.Cd) ? (sb.wm_off + (cd0 + row) * sb.Kpad + chunk * 8) * 2 : OOB;
+        voffb[j] = (cd0 + row < g.e.Cd) ? (sb.wm_off + (cd0 + row) * sb.Kpad + chunk * 8) * 2 : OOB;
         tailok |= (tail_c0 + chunk * 8 < g.Cs ? 1u : 0u) << (8 + j);
     }
     // descriptor base = src - one row - one pixel, so the scalar tap offset (dh+1, dw+1) is never negative
@@ -206,84 +200,29 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
     // ---- epilogue: lane holds channels c..c+3 of pixel (tile pixel prow + i*16 + fr)
     const int cq = fg * 4;
     float bv[WN][4];
+    bias_blocks<WN>(bias, cd0 + crow, cq, g.e, bv);
+    LinearPixels px;
+    px.start(m0 + prow + fr, sb.npix, sb.Wg, sb.Hg);
 #pragma unroll
-    for (int j = 0; j < WN; ++j) {
-        const int c = cd0 + crow + j * 16 + cq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bv[j][r] = (bias != nullptr && c < g.Cd) ? bias[c + r] : 0.f;
-    }
-    {
-        int q = m0 + prow + fr;
-        const unsigned qq = q < sb.npix ? q : 0;
-        const unsigned t2 = qq / (unsigned)sb.Wg;
-        int b = (int)(qq - t2 * sb.Wg);
-        int n = (int)(t2 / (unsigned)sb.Hg);
-        int a = (int)t2 - n * sb.Hg;
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-            const bool live = q < sb.npix;
-            const long pix = live ? ((long)n * g.Hd + a * g.ostep + sb.ooff_h) * (long)g.Wd + b * g.ostep + sb.ooff_w : 0;
-            store_pixel_blocks<T, WN, ACC>(g, acc[i], bv, dst, pix, live, cd0 + crow, cq, lane);
-            q += 16;
-            b += 16;
-            while (b >= sb.Wg) {
-                b -= sb.Wg;
-                if (++a == sb.Hg) { a = 0; ++n; }
-            }
-        }
+    for (int i = 0; i < WM; ++i) {
+        store_pixel_blocks<T, WN, ACC>(g.e, acc[i], bv, dst, px.pix(g.Hd, g.Wd, g.ostep, sb.ooff_h, sb.ooff_w), px.live(), cd0 + crow, cq, lane);
+        px.advance16();
     }
 
-    // ---- optional BatchNorm batch statistics of the stored (rounded) values, as in k_conv_mfma
-    float* const stats = g.stats;
-    if (stats != nullptr) {
+    // ---- optional BatchNorm batch statistics (rows past the last pixel hold 0)
+    if (g.e.stats != nullptr) {
         __builtin_amdgcn_s_barrier();                         // every wave is past its last fragment read and its DMA drain
-        float* sacc = reinterpret_cast<float*>(smem);         // [2][BN]
-        for (int t = tid; t < 2 * BN; t += 256) sacc[t] = 0.f;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            float s[4] = {0.f, 0.f, 0.f, 0.f}, q2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = to_f<T>(from_f<T>(acc[i][j][r]));     // rows past the last pixel hold 0
-                    s[r] += v;
-                    q2[r] += v * v;
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[r] = row16_sum(s[r]);
-                q2[r] = row16_sum(q2[r]);
-            }
-            if (fr == 0) {
-                const int cl = crow + j * 16 + cq;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    atomicAdd(&sacc[cl + r], s[r]);
-                    atomicAdd(&sacc[BN + cl + r], q2[r]);
-                }
-            }
-        }
-        __syncthreads();
-        float* o = stats + (long)(blockIdx.x & 7) * 2 * g.Cd;
-        for (int t = tid; t < BN; t += 256)
-            if (cd0 + t < g.Cd) {
-                atomicAdd(o + cd0 + t, sacc[t]);
-                atomicAdd(o + g.Cd + cd0 + t, sacc[BN + t]);
-            }
+        conv_stats_epilogue<T, WM, WN>(acc, reinterpret_cast<float*>(smem), BN, g.e.stats, cd0, g.e.Cd, crow, cq, fr, tid, 256);
     }
 }
 
 template <typename T, int RB, int WGM, int WGN, int WM, int WN, int NST>
 void launch_ring_t(const RingGeom& g, int nwg, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
                    hipStream_t st) {
-    if (accumulate)
-        hipLaunchKernelGGL((k_conv_ring<T, RB, WGM, WGN, WM, WN, NST, true>), dim3(nwg), dim3(256), 0, st, g, (const T*)src,
-                           (const T*)wm, bias, (T*)dst);
-    else
-        hipLaunchKernelGGL((k_conv_ring<T, RB, WGM, WGN, WM, WN, NST, false>), dim3(nwg), dim3(256), 0, st, g, (const T*)src,
-                           (const T*)wm, bias, (T*)dst);
+    with_acc(accumulate, [&](auto acc) {
+        hipLaunchKernelGGL((k_conv_ring<T, RB, WGM, WGN, WM, WN, NST, decltype(acc)::value>), dim3(nwg), dim3(256), 0, st, g,
+                           (const T*)src, (const T*)wm, bias, (T*)dst);
+    });
 }
 
 template <typename T>
@@ -328,11 +267,9 @@ int ring_conv_launch(const ConvGeom* gs, int n, const RingTile& t, const long* w
     if (n < 1 || n > 4 || wm_elems >= (1L << 30)) return YOLO_ERR_ARG;
     const ConvGeom& g0 = gs[0];
     RingGeom d;
-    d.N = g0.N; d.Hs = g0.Hs; d.Ws = g0.Ws; d.Cs = g0.Cs; d.lds = g0.lds; d.Hd = g0.Hd; d.Wd = g0.Wd; d.Cd = g0.Cd; d.ldd = g0.ldd;
-    d.ostep = g0.ostep; d.sstride = g0.sstride; d.stats = g0.stats;
-    d.acc2 = g0.acc2; d.ld2 = g0.ld2;
-    d.act = g0.act; d.res = g0.res; d.ldr = g0.ldr;
-    d.wide = to_dev(g0).wide;
+    d.N = g0.N; d.Hs = g0.Hs; d.Ws = g0.Ws; d.Cs = g0.Cs; d.lds = g0.lds; d.Hd = g0.Hd; d.Wd = g0.Wd;
+    d.ostep = g0.ostep; d.sstride = g0.sstride;
+    d.e = to_epi(g0);
     d.spt = (g0.Cs + t.bk - 1) / t.bk;
     d.ntile_n = (g0.Cd + t.bn - 1) / t.bn;
     d.wm_elems = (int)wm_elems;

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
     // ---- DMA sources: fixed per-lane byte offsets (swizzle applied to the SOURCE chunk, the LDS image is lane-linear),
     // one scalar offset per chunk / step, out of range = zeros
     const int shift = (g.Ws + 1) * g.lds;
-    const int a_bytes = (g.N * g.Hs * g.Ws * g.lds + shift) * 2, w_bytes = g.Cd * g.Kpad * 2;
+    const int a_bytes = (g.N * g.Hs * g.Ws * g.lds + shift) * 2, w_bytes = g.e.Cd * g.Kpad * 2;
     int hvoff[HP], wvoff[DW];
 #pragma unroll
     for (int i = 0; i < HP; ++i) {
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
         const int rs = (wave * DW + j) * 16 + (lane >> 2);   // row of the stage: (tap of the step, channel)
         const int tl = rs / BN, row = rs - tl * BN;
         const int kseg = (lane & 3) ^ ((-(row >> 2)) & 3);   // k_conv_mfma's swizzle
-        wvoff[j] = (tl < 3 && cd0 + row < g.Cd && kseg * 8 < g.Cs) ? ((cd0 + row) * g.Kpad + tl * g.Cs + kseg * 8) * 2 : OOB;
+        wvoff[j] = (tl < 3 && cd0 + row < g.e.Cd && kseg * 8 < g.Cs) ? ((cd0 + row) * g.Kpad + tl * g.Cs + kseg * 8) * 2 : OOB;
     }
     const int nchunk = (g.Cs + BK - 1) / BK, nit = nchunk * 3;   // Cs is a multiple of 32, or 16 (one half-filled chunk)
     auto issue_halo = [&](int chunk) {                       // chunks past the end: zero-size descriptor, same piece count
@@ -165,24 +165,18 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
     }
     if (chunk < nchunk) { step(c0{}, c0{}, chunk); step(c1{}, c0{}, chunk); step(c2{}, c0{}, chunk); }
     rows_wait<0>();                                          // the zero-fill pieces issued past the end of K
-    __syncthreads();
-    T* const wl = reinterpret_cast<T*>(rows_smem);           // LDS is idle from here on (statistics scratch)
+    __syncthreads();                                         // LDS is idle from here on (statistics scratch)
 
     // ---- epilogue: lane holds channels c..c+3 of its pixel of tile i
     const int cq = fg * 4;
     float bv[WN][4];
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-        const int c = cd0 + crow + j * 16 + cq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bv[j][r] = (bias != nullptr && c < g.Cd) ? bias[c + r] : 0.f;
-    }
+    bias_blocks<WN>(bias, cd0 + crow, cq, g.e, bv);
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         const int p = (wgm * 5 + i) * 16 + fr, pr = p / W, pc = p - pr * W;
         const int oy = y0 + pr, ox = x0 + pc;
         const bool live = oy < g.Hg && ox < g.Wg;
-        store_pixel_blocks<T, WN, ACC>(g, acc[i], bv, dst, live ? ((long)n * g.Hd + oy) * (long)g.Wd + ox : 0, live, cd0 + crow, cq, lane);
+        store_pixel_blocks<T, WN, ACC>(g.e, acc[i], bv, dst, live ? ((long)n * g.Hd + oy) * (long)g.Wd + ox : 0, live, cd0 + crow, cq, lane);
         if (!live) {
             // pixels outside the map must not reach the statistics
 #pragma unroll
@@ -190,63 +184,24 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
         }
     }
 
-    // ---- optional BatchNorm batch statistics of the stored (rounded) values, as in k_conv_mfma
-    float* const stats = g.stats;
-    if (stats != nullptr) {
-        float* sacc = reinterpret_cast<float*>(wl);          // [2][BN]; LDS is idle after the K loop (last barrier passed)
-        for (int t = tid; t < 2 * BN; t += NTHR) sacc[t] = 0.f;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            float s[4] = {0.f, 0.f, 0.f, 0.f}, q2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = to_f<T>(from_f<T>(acc[i][j][r]));
-                    s[r] += v;
-                    q2[r] += v * v;
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[r] = row16_sum(s[r]);
-                q2[r] = row16_sum(q2[r]);
-            }
-            if (fr == 0) {
-                const int cl = crow + j * 16 + cq;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    atomicAdd(&sacc[cl + r], s[r]);
-                    atomicAdd(&sacc[BN + cl + r], q2[r]);
-                }
-            }
-        }
-        __syncthreads();
-        float* o = stats + (long)(blockIdx.x & 7) * 2 * g.Cd;
-        for (int t = tid; t < BN; t += NTHR)
-            if (cd0 + t < g.Cd) {
-                atomicAdd(o + cd0 + t, sacc[t]);
-                atomicAdd(o + g.Cd + cd0 + t, sacc[BN + t]);
-            }
-    }
+    // ---- optional BatchNorm batch statistics
+    if (g.e.stats != nullptr)
+        conv_stats_epilogue<T, 5, WN>(acc, reinterpret_cast<float*>(rows_smem), BN, g.e.stats, cd0, g.e.Cd, crow, cq, fr, tid, NTHR);
 }
 
 template <typename T, int W, int WGM, int NWAVE, int WN, int NST>
 int launch_rows(const GeomDev& d, const void* src, const void* wm, const float* bias, void* dst, int accumulate, hipStream_t st) {
     constexpr int R = WGM * 80 / W, BN = (NWAVE / WGM) * WN * 16, HPX = (R + 2) * (W == 16 ? 18 : W + 8);
     constexpr size_t lds = 2 * (size_t)(NWAVE * (((HPX + 15) / 16 + NWAVE - 1) / NWAVE)) * 1024 + (size_t)NST * NWAVE * ((3 * BN / 16 + NWAVE - 1) / NWAVE) * 1024;
-    const int th = (d.Hg + R - 1) / R, tw = W == 16 ? (d.Wg + 15) / 16 : 1, tn = (d.Cd + BN - 1) / BN;
+    const int th = (d.Hg + R - 1) / R, tw = W == 16 ? (d.Wg + 15) / 16 : 1, tn = (d.e.Cd + BN - 1) / BN;
     const dim3 grid((unsigned)(d.N * th * tw * tn));
-    if (accumulate) {
+    return with_acc(accumulate, [&](auto acc) {
+        constexpr bool ACC = decltype(acc)::value;
         static unsigned long long done = 0;         // per instantiation: devices that have the attribute
-        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_conv_rows<T, W, WGM, NWAVE, WN, NST, true>), lds, done)) return e;
-        hipLaunchKernelGGL((k_conv_rows<T, W, WGM, NWAVE, WN, NST, true>), grid, dim3(64 * NWAVE), lds, st, d, (const T*)src, (const T*)wm, bias, (T*)dst, th, tw, tn);
-    } else {
-        static unsigned long long done = 0;         // per instantiation: devices that have the attribute
-        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_conv_rows<T, W, WGM, NWAVE, WN, NST, false>), lds, done)) return e;
-        hipLaunchKernelGGL((k_conv_rows<T, W, WGM, NWAVE, WN, NST, false>), grid, dim3(64 * NWAVE), lds, st, d, (const T*)src, (const T*)wm, bias, (T*)dst, th, tw, tn);
-    }
-    return YOLO_LAUNCH_CHECK();
+        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_conv_rows<T, W, WGM, NWAVE, WN, NST, ACC>), lds, done)) return e;
+        hipLaunchKernelGGL((k_conv_rows<T, W, WGM, NWAVE, WN, NST, ACC>), grid, dim3(64 * NWAVE), lds, st, d, (const T*)src, (const T*)wm, bias, (T*)dst, th, tw, tn);
+        return YOLO_LAUNCH_CHECK();
+    });
 }
 
 }  // namespace

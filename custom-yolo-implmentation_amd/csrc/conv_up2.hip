@@ -20,13 +20,10 @@ namespace {
 constexpr int UPW = 17;        // patch width (16 + 1)
 
 struct Up2Geom {
-    int N, Hs, Ws, Cs, lds, Hd, Wd, Cd, ldd;
+    int N, Hs, Ws, Cs, lds, Hd, Wd;
     int wm_off[4], Kpad[4];    // class matrices inside the packed buffer (elements)
     int wm_elems;
-    // what store_pixel_blocks reads (no bias / activation / second source in a data gradient of this kind)
-    int wide, act, ldr, ld2;
-    const void* res;
-    const void* acc2;
+    ConvEpi e;                 // no bias / activation / second source / statistics in a data gradient of this kind
 };
 
 // the nine (class, tap) products in step order; taps of a class in conv_taps' order: (dh, dw) = (t / nw, t % nw)
@@ -89,7 +86,7 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
         const int rs = (wave * DW + j) * 16 + (lane >> 2);   // row of the stage: (tile of the step, channel)
         const int pl = rs / BN, row = rs - pl * BN;
         const int kseg = (lane & 3) ^ ((-(row >> 2)) & 3);
-        const bool ok = pl < 3 && cd0 + row < g.Cd;
+        const bool ok = pl < 3 && cd0 + row < g.e.Cd;
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
             const int p = 3 * s + pl;                        // pl is a run-time value: the (class, tap) of product 3s + pl
@@ -191,7 +188,8 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
     const int cq = fg * 4;
     const int b = x0 + fr;
     const int Hg = g.Hd >> 1, Wg = g.Wd >> 1;
-    const float zero_bias[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    float zero_bias[2][4];
+    bias_blocks<2>(nullptr, cd0 + crow, cq, g.e, zero_bias);
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
         const int a = y0 + wgm * WM + i;
@@ -199,7 +197,7 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const long pix = live ? ((long)n * g.Hd + 2 * a + (c >> 1)) * (long)g.Wd + 2 * b + (c & 1) : 0;
-            store_pixel_blocks<T, 2, ACC>(g, acc[c][i], zero_bias, dst, pix, live, cd0 + crow, cq, lane);
+            store_pixel_blocks<T, 2, ACC>(g.e, acc[c][i], zero_bias, dst, pix, live, cd0 + crow, cq, lane);
         }
     }
 }
@@ -209,18 +207,15 @@ int launch_up2(const Up2Geom& d, const void* src, const void* wm, void* dst, int
     constexpr int NW = (TH / WM) * (BN / 32), NTHR = NW * 64;
     constexpr int HP = (((TH + 1) * UPW + 15) / 16 + NW - 1) / NW, DW = (3 * BN / 16 + NW - 1) / NW;
     constexpr size_t lds = (size_t)(2 * NW * HP + NST * NW * DW) * 1024;
-    const int th = (d.Hs + TH - 1) / TH, tw = (d.Ws + 15) / 16, tn = (d.Cd + BN - 1) / BN;
+    const int th = (d.Hs + TH - 1) / TH, tw = (d.Ws + 15) / 16, tn = (d.e.Cd + BN - 1) / BN;
     const dim3 grid((unsigned)(d.N * th * tw * tn));
-    if (accumulate) {
+    return with_acc(accumulate, [&](auto acc) {
+        constexpr bool ACC = decltype(acc)::value;
         static unsigned long long done = 0;         // per instantiation: devices that have the attribute
-        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_dgrad2_patch<T, TH, BN, WM, NST, true>), lds, done)) return e;
-        hipLaunchKernelGGL((k_dgrad2_patch<T, TH, BN, WM, NST, true>), grid, dim3(NTHR), lds, st, d, (const T*)src, (const T*)wm, (T*)dst, th, tw, tn);
-    } else {
-        static unsigned long long done = 0;         // per instantiation: devices that have the attribute
-        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_dgrad2_patch<T, TH, BN, WM, NST, false>), lds, done)) return e;
-        hipLaunchKernelGGL((k_dgrad2_patch<T, TH, BN, WM, NST, false>), grid, dim3(NTHR), lds, st, d, (const T*)src, (const T*)wm, (T*)dst, th, tw, tn);
-    }
-    return YOLO_LAUNCH_CHECK();
+        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_dgrad2_patch<T, TH, BN, WM, NST, ACC>), lds, done)) return e;
+        hipLaunchKernelGGL((k_dgrad2_patch<T, TH, BN, WM, NST, ACC>), grid, dim3(NTHR), lds, st, d, (const T*)src, (const T*)wm, (T*)dst, th, tw, tn);
+        return YOLO_LAUNCH_CHECK();
+    });
 }
 
 }  // namespace
@@ -253,12 +248,12 @@ int up2_conv_launch(const ConvGeom* gs, int variant, const long* wm_off, long wm
         (reinterpret_cast<uintptr_t>(dst) & 7))
         return YOLO_ERR_ARG;
     Up2Geom d;
-    d.N = g.N; d.Hs = g.Hs; d.Ws = g.Ws; d.Cs = g.Cs; d.lds = g.lds; d.Hd = g.Hd; d.Wd = g.Wd; d.Cd = g.Cd; d.ldd = g.ldd;
+    d.N = g.N; d.Hs = g.Hs; d.Ws = g.Ws; d.Cs = g.Cs; d.lds = g.lds; d.Hd = g.Hd; d.Wd = g.Wd;
     for (int c = 0; c < 4; ++c) { d.wm_off[c] = (int)wm_off[c]; d.Kpad[c] = gs[c].Kpad; }
     d.wm_elems = (int)wm_elems;
     // (Round 3: with the 16-byte exchange path this kernel returned a whole workgroup tile of parity class (1,1) short of one
     // (chunk, tap) product in a few launches of a hundred.  Not the stores: the counted waits of the ring, see up2_wait.)
-    d.wide = conv_wide_flag(); d.act = 0; d.res = nullptr; d.ldr = 0; d.acc2 = nullptr; d.ld2 = 0;
+    d.e = to_epi(g);        // a data gradient: no activation, residual or statistics; up2_conv_eligible refuses a second source
     if (g.N * g.Hs * g.Ws == 0) return YOLO_OK;
 #define UP2_T(T_)                                                                                       \
     return variant == 16 ? launch_up2<T_, 16, 32, 4, 3>(d, src, wm, dst, accumulate, st)                \

@@ -67,7 +67,7 @@ __global__ void k_stem_unpack_dw(const float* __restrict__ dw32, int Cout, P* __
 // columns each) are staged once in LDS, one 16-byte load per lane = one row segment per wave instruction; every lane then gathers its MFMA B fragment
 // (8 consecutive k of one pixel; k = ci*9 + kh*3 + kw, so row = k/3 and column offset = k%3) from LDS and the A
 // fragments (weights [Cout][32], L2-resident) from global memory: one 16x16x32 MFMA per (16 channels x 16 pixels).
-// Epilogue as k_conv_mfma: 8-byte channel groups per lane, BatchNorm batch statistics of the rounded values.
+// Epilogue: 8-byte channel groups per lane, BatchNorm batch statistics of the rounded values (the pieces of conv_dev.h).
 constexpr int STEM_SEG = 128;
 constexpr int STEM_ROWW = 2 * STEM_SEG + 1;
 constexpr int STEM_IR = 5;          // input rows per channel for TWO output rows (the middle one is shared)
@@ -124,13 +124,13 @@ __global__ __launch_bounds__(256) void k_stem_conv(const float* __restrict__ img
             rows[r][3 + c] = ok ? img[(((long)n * 3 + ci) * H + ih) * (long)W + iw] : 0.f;
         }
     }
-    for (int c = tid; c < 2 * 16 * CT; c += 256) (&sacc[0][0])[c] = 0.f;
+    stats_zero(&sacc[0][0], 2 * 16 * CT, tid, 256);         // before the barrier that publishes the rows: the statistics need no extra one
     frag a[CT];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) a[ct] = *reinterpret_cast<const frag*>(wp + (long)(ct * 16 + fr) * 32 + kg * 8);
     __syncthreads();
     // a wave owns four 16-pixel tiles: tile id wave*4 + i = (output row j) * 8 + (tile within the 128-pixel segment)
-    f32x4 acc[CT][4];
+    f32x4 acc[4][CT];                                    // [pixel tile][channel block]
     bool live[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_stem_conv(const float* __restrict__ img
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            acc[ct][i] = ops::mma(a[ct], b, z);
+            acc[i][ct] = ops::mma(a[ct], b, z);
         }
     }
     // lane holds channels ct*16 + kg*4 .. +3 of its tile's pixel fr
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_stem_conv(const float* __restrict__ img
         for (int ct = 0; ct < CT; ++ct) {
             float v[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = acc[ct][i][r];
+            for (int r = 0; r < 4; ++r) v[r] = acc[i][ct][r];
             if (bias != nullptr) {                              // fused inference (BatchNorm folded in): act(conv + b)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] += bias[ct * 16 + kg * 4 + r];
@@ -172,37 +172,10 @@ __global__ __launch_bounds__(256) void k_stem_conv(const float* __restrict__ img
             store_pack<T, 4>(drow + ct * 16 + kg * 4, v);
         }
     }
-    if (stats != nullptr) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            float s[4] = {0.f, 0.f, 0.f, 0.f}, q2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = to_f<T>(from_f<T>(acc[ct][i][r]));      // pixels past the row / image end hold 0
-                    s[r] += v;
-                    q2[r] += v * v;
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[r] = row16_sum(s[r]);
-                q2[r] = row16_sum(q2[r]);
-            }
-            if (fr == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    atomicAdd(&sacc[0][ct * 16 + kg * 4 + r], s[r]);
-                    atomicAdd(&sacc[1][ct * 16 + kg * 4 + r], q2[r]);
-                }
-            }
-        }
+    if (stats != nullptr) {                                 // pixels past the row / image end hold 0
+        stats_lane_sums<T, 4, CT>(acc, &sacc[0][0], 16 * CT, 0, kg * 4, fr);
         __syncthreads();
-        float* o = stats + (long)(blockIdx.x & 7) * 2 * Cout;
-        for (int c = tid; c < 16 * CT; c += 256) {
-            atomicAdd(o + c, sacc[0][c]);
-            atomicAdd(o + Cout + c, sacc[1][c]);
-        }
+        stats_flush(&sacc[0][0], 16 * CT, stats, 0, Cout, tid, 256);
     }
 }
 

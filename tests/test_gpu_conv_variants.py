@@ -326,6 +326,57 @@ def test_rows_kernel_f16(force, cin, cout, h, w, plan):
                        dtype=HF)
 
 
+# ---- the statistics epilogue ADDS into its accumulator and stays inside it.  assert_stats on a zeroed accumulator of its
+# own cannot tell an overwrite from an add, nor see a write past the [8][2][cout] slice.  cout 72: a partial second channel
+# tile; 7 x 11 / 9 x 20 maps: a partial last pixel tile.  (tune arguments of yolo_conv_tune_set, h, w, plan)
+STATS_ADD_CASES = [
+    pytest.param((32, -1, 0, 0, 0, 0, 0, 0), 7, 11, 1032, id="gather-bn32-registers"),
+    pytest.param((32, -1, 0, 1, 0, 0, 0, 0), 7, 11, 1032, id="gather-bn32-dma"),
+    pytest.param((128, -1, 0, 0, 0, 0, 0, 0), 7, 11, 1128, id="gather-bn128-registers"),
+    pytest.param((128, -1, 0, 1, 0, 0, 0, 0), 7, 11, 1128, id="gather-bn128-dma"),
+    pytest.param((64, -1, 0, -1, 1, 64, 3, 64), 7, 11, ring_plan(64, 64), id="ring-64x64"),
+    pytest.param((128, -1, 0, -1, 1, 128, 2, 64), 7, 11, ring_plan(128, 128), id="ring-128x128"),
+    pytest.param((0, -1, 1, -1, -1, 0, 0, 0), 7, 11, 2001, id="halo-1"),
+    pytest.param((0, -1, 4, -1, -1, 0, 0, 0), 7, 11, 2004, id="halo-4"),
+    pytest.param((0, -1, 6, -1, -1, 0, 0, 0), 9, 20, rows_plan(6, 72), id="rows-full-row"),
+    pytest.param((0, -1, 14, -1, -1, 0, 0, 0), 7, 11, rows_plan(14, 72), id="rows-16-wide"),
+    pytest.param(None, 18, 22, None, id="stem"),
+]
+STATS_GUARD, STATS_SENTINEL, STATS_PREFILL = 64, -777.25, 0.5
+
+
+@pytest.mark.parametrize("tune,h,w,plan", STATS_ADD_CASES)
+def test_statistics_epilogue_adds_into_its_slice_only(tune, h, w, plan):
+    """One forward with statistics per kernel family; the accumulator is a [8][2][cout] slice, pre-filled with 0.5, of a
+    larger fp32 buffer whose guard regions on both sides hold a sentinel.  The guards must come back bit-unchanged, and the
+    sum over the replicas minus 8 * 0.5 must be the sums of the stored y at assert_stats' bound (2e-5 of the mass)."""
+    o = ops()
+    if tune is None:                                 # the fused stem: fp32 NCHW image, 3 -> 32
+        cout = 32
+        img = rnd((2, 3, h, w), 41, dtype=torch.float32).to(DEV)
+        assert o.stem_conv_eligible(img, BF, cout)
+        wp = o.stem_pack_weights(rnd((cout, 3, 3, 3), 42, 0.2, torch.float32).to(DEV), BF)
+        run = lambda acc: o.stem_conv_fwd(img, wp, cout, BF, acc)
+    else:
+        cin, cout = 64, 72
+        lib().call("yolo_conv_tune_set", *tune)
+        got = lib().query("yolo_conv2d_plan", 2, h, w, cin, h, w, cout, 3, 1, 0, 0, lib().BF16)
+        assert got == plan, f"test does not reach the variant it is written for: plan {got}, wanted {plan}"
+        xd, _, _ = on_dev(rnd((2, cin, h, w), 43))
+        wp = o.pack_weights(rnd((cout, cin, 3, 3), 44, (cin * 9) ** -0.5).float().to(DEV), 3, 1, 0, BF)
+        run = lambda acc: o.conv_fwd(xd, wp, None, cout, 3, 1, acc)
+    n_acc = o.BN_REPL * 2 * cout
+    buf = torch.full((STATS_GUARD + n_acc + STATS_GUARD,), STATS_SENTINEL, dtype=torch.float32, device=DEV)
+    acc = buf[STATS_GUARD:STATS_GUARD + n_acc]
+    acc.fill_(STATS_PREFILL)
+    y = run(acc)
+    guards = torch.cat([buf[:STATS_GUARD], buf[STATS_GUARD + n_acc:]]).cpu()
+    assert torch.equal(guards.view(torch.int32), torch.full_like(guards, STATS_SENTINEL).view(torch.int32)), \
+        "the statistics epilogue wrote outside its [8][2][cout] accumulator"
+    added = acc.double().view(o.BN_REPL, 2, cout).sum(0) - o.BN_REPL * STATS_PREFILL
+    sc.assert_stats(added, y, f"statistics added to a pre-filled accumulator, {h}x{w} plan {plan}")
+
+
 # ---- the fused inference epilogue (bias, SiLU, residual) under every forced forward variant, bf16 and f16 (config 5 runs
 # exactly these instantiations; yolo_conv2d_fwd_act goes through the same launcher, so yolo_conv_tune_set steers it)
 @pytest.mark.parametrize("dtype", DTYPES)
