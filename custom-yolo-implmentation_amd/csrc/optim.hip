@@ -62,6 +62,30 @@ __device__ __forceinline__ void ema_coef(const double* ectl, float& df, float& o
     omd = (float)(1.0 - d);
 }
 
+// The job that owns this workgroup's chunk: the last record with cstart <= blockIdx.x (one thread per workgroup asks).
+__device__ __forceinline__ int job_of_block(const AdamJob* __restrict__ jobs, int njobs) {
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].cstart <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The EMA tail of the step kernels and k_ema_lerp: e = d*e + (1-d)*w, w the parameter AS STORED (as_stored: a bf16 / f16
+// parameter's rounded value, so the average is one of the observable weights).
+__device__ __forceinline__ float ema_elem(float e, float w, float df, float omd) { return __fmaf_rn(df, e, __fmul_rn(omd, w)); }
+__device__ __forceinline__ float as_stored(float x, int dt) {
+    return dt == YOLO_F32 ? x : dt == YOLO_BF16 ? to_f<bf16_t>(from_f<bf16_t>(x)) : to_f<f16_t>(from_f<f16_t>(x));
+}
+__device__ __forceinline__ void ema_packet(float* __restrict__ ema, long i, const float* w, float df, float omd) {
+    float4 e = *reinterpret_cast<float4*>(ema + i);
+    float* ep = &e.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ep[k] = ema_elem(ep[k], w[k], df, omd);
+    *reinterpret_cast<float4*>(ema + i) = e;
+}
+
 // step += 1 (and the group's EMA update count, found through the first record) unless the scaler found an overflow
 // (one thread; the main kernel reads the updated values)
 __global__ void k_adamw_tick(float* __restrict__ step, const float* __restrict__ found_inf, const AdamJob* __restrict__ jobs) {
@@ -81,12 +105,7 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
     __shared__ int sj;
     __shared__ float sc[9];                     // b1, 1-b1, b2, 1-b2, step_size, 1/sqrt(bc2), decay, ema d, ema 1-d
     if (threadIdx.x == 0) {
-        int lo = 0, hi = njobs - 1;
-        while (lo < hi) {                       // last job with cstart <= blockIdx.x
-            const int mid = (lo + hi + 1) >> 1;
-            if (jobs[mid].cstart <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
-        }
-        sj = lo;
+        const int lo = sj = job_of_block(jobs, njobs);
         const double lr = hyper[0], b1d = hyper[1], b2d = hyper[2], wd = hyper[4], t = (double)*step;
         const double bc1 = 1.0 - pow(b1d, t), bc2 = 1.0 - pow(b2d, t);
         sc[0] = (float)b1d; sc[1] = (float)(1.0 - b1d); sc[2] = (float)b2d; sc[3] = (float)(1.0 - b2d);
@@ -117,13 +136,7 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
             *reinterpret_cast<float4*>((float*)j.p + i) = p;
             *reinterpret_cast<float4*>(j.m + i) = m;
             *reinterpret_cast<float4*>(j.v + i) = v;
-            if (ema != nullptr) {
-                float4 e = *reinterpret_cast<float4*>(ema + i);
-                float* ep = &e.x;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) ep[k] = __fmaf_rn(df, ep[k], __fmul_rn(omd, pp[k]));
-                *reinterpret_cast<float4*>(ema + i) = e;
-            }
+            if (ema != nullptr) ema_packet(ema, i, pp, df, omd);
         }
         return;
     }
@@ -133,12 +146,75 @@ __global__ __launch_bounds__(256) void k_adamw(const AdamJob* __restrict__ jobs,
         j.m[i] = m;
         j.v[i] = v;
         st_any(j.p, j.p_dtype, i, pv);
-        if (ema != nullptr) {
-            // the parameter as stored: a bf16 / f16 parameter's rounded value, so the average is one of the observable weights
-            const float w = j.p_dtype == YOLO_F32 ? pv : j.p_dtype == YOLO_BF16 ? to_f<bf16_t>(from_f<bf16_t>(pv))
-                                                                                 : to_f<f16_t>(from_f<f16_t>(pv));
-            ema[i] = __fmaf_rn(df, ema[i], __fmul_rn(omd, w));
+        if (ema != nullptr) ema[i] = ema_elem(ema[i], as_stored(pv, j.p_dtype), df, omd);
+    }
+}
+
+// ---- SGD with momentum (torch.optim.SGD: dampening 0, coupled weight decay, optional Nesterov, maximize False) over the
+// same job table, v null and m the momentum buffer:
+//   d = wd*p + g*gs;  buf = mu*buf + d;  n = nesterov ? mu*buf + d : buf;  p = p - lr*n
+// Four fused multiply-adds and the unscale: one rounding each.  A zero buffer makes the first step buf = d, as torch's
+// clone does.  The packet path and the any-dtype path share it, so identical inputs give identical bits on either.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float gs, float& buf, float lr, float mu, float wd, bool nesterov) {
+    const float d = __fmaf_rn(wd, p, __fmul_rn(g, gs));
+    buf = __fmaf_rn(mu, buf, d);
+    const float n = nesterov ? __fmaf_rn(mu, buf, d) : buf;
+    p = __fmaf_rn(-lr, n, p);
+}
+
+// hyper = [lr, momentum, weight_decay, nesterov (0 / 1), warmup_steps W, warmup_momentum mu0, warmup_lr_scale s0] as DOUBLES.
+// Warm-up, per iteration and on the device: with t = *step after the tick (1, 2, ...) and f = (t - 1) / W, a step with
+// t <= W runs at lr*(s0 + (1 - s0)*f) and mu0 + (mu - mu0)*f; later steps and W = 0 see lr and mu themselves.  A step
+// skipped on found_inf does not tick, so it does not advance the warm-up either.
+__global__ __launch_bounds__(256) void k_sgd(const AdamJob* __restrict__ jobs, int njobs, const double* __restrict__ hyper,
+                                             const float* __restrict__ step, const float* __restrict__ grad_scale,
+                                             const float* __restrict__ found_inf, const float* __restrict__ clip) {
+    if (found_inf != nullptr && *found_inf != 0.f) return;
+    __shared__ int sj;
+    __shared__ float sc[5];                     // lr_t, mu_t, wd, ema d, ema 1-d
+    if (threadIdx.x == 0) {
+        const int lo = sj = job_of_block(jobs, njobs);
+        double lr = hyper[0], mu = hyper[1];
+        const double W = hyper[4], mu0 = hyper[5], s0 = hyper[6], t = (double)*step;
+        if (W > 0.0 && t <= W) {
+            const double f = (t - 1.0) / W;
+            lr = lr * (s0 + (1.0 - s0) * f);
+            mu = mu0 + (mu - mu0) * f;
         }
+        sc[0] = (float)lr; sc[1] = (float)mu; sc[2] = (float)hyper[2];
+        sc[3] = 0.f; sc[4] = 0.f;
+        if (jobs[lo].e != nullptr && jobs[lo].ectl != nullptr) ema_coef(jobs[lo].ectl, sc[3], sc[4]);
+    }
+    __syncthreads();
+    const AdamJob j = jobs[sj];
+    const float lr = sc[0], mu = sc[1], wd = sc[2], df = sc[3], omd = sc[4];
+    const bool nesterov = hyper[3] != 0.0;
+    float* const ema = j.ectl != nullptr ? j.e : nullptr;
+    float gs = grad_scale ? 1.f / *grad_scale : 1.f;            // as in k_adamw: unscale and clip in flight
+    if (clip != nullptr) gs *= clip[2];
+    const long base = ((long)blockIdx.x - j.cstart) * CHUNK;
+    if (j.p_dtype == YOLO_F32 && j.g_dtype == YOLO_F32 && (j.n & 3) == 0 &&
+        ((reinterpret_cast<uintptr_t>(j.p) | reinterpret_cast<uintptr_t>(j.g) | reinterpret_cast<uintptr_t>(j.m) |
+          reinterpret_cast<uintptr_t>(ema)) & 15) == 0) {
+        for (long i = base + threadIdx.x * 4L; i < base + CHUNK && i < j.n; i += 256 * 4) {
+            float4 p = *reinterpret_cast<float4*>((float*)j.p + i);
+            const float4 g = *reinterpret_cast<const float4*>((const float*)j.g + i);
+            float4 m = *reinterpret_cast<float4*>(j.m + i);
+            float* pp = &p.x; const float* gp = &g.x; float* mp = &m.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sgd_elem(pp[k], gp[k], gs, mp[k], lr, mu, wd, nesterov);
+            *reinterpret_cast<float4*>((float*)j.p + i) = p;
+            *reinterpret_cast<float4*>(j.m + i) = m;
+            if (ema != nullptr) ema_packet(ema, i, pp, df, omd);
+        }
+        return;
+    }
+    for (long i = base + threadIdx.x; i < base + CHUNK && i < j.n; i += 256) {
+        float pv = ld_any(j.p, j.p_dtype, i), m = j.m[i];
+        sgd_elem(pv, ld_any(j.g, j.g_dtype, i), gs, m, lr, mu, wd, nesterov);
+        j.m[i] = m;
+        st_any(j.p, j.p_dtype, i, pv);
+        if (ema != nullptr) ema[i] = ema_elem(ema[i], as_stored(pv, j.p_dtype), df, omd);
     }
 }
 
@@ -151,12 +227,7 @@ __global__ __launch_bounds__(256) void k_ema_lerp(const AdamJob* __restrict__ jo
     __shared__ int sj;
     __shared__ float sc[2];
     if (threadIdx.x == 0) {
-        int lo = 0, hi = njobs - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (jobs[mid].cstart <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
-        }
-        sj = lo;
+        sj = job_of_block(jobs, njobs);
         ema_coef(ectl, sc[0], sc[1]);
     }
     __syncthreads();
@@ -165,7 +236,7 @@ __global__ __launch_bounds__(256) void k_ema_lerp(const AdamJob* __restrict__ jo
     if (j.e == nullptr) return;
     const long base = ((long)blockIdx.x - j.cstart) * CHUNK;
     for (long i = base + threadIdx.x; i < base + CHUNK && i < j.n; i += 256)
-        j.e[i] = __fmaf_rn(df, j.e[i], __fmul_rn(omd, ld_any(j.p, j.p_dtype, i)));
+        j.e[i] = ema_elem(j.e[i], ld_any(j.p, j.p_dtype, i), df, omd);
 }
 
 // ---- global gradient norm (torch.nn.utils.clip_grad_norm_, norm_type 2; the reference's config.yaml carries
@@ -181,12 +252,7 @@ __global__ __launch_bounds__(256) void k_grad_sqnorm(const AdamJob* __restrict__
     __shared__ int sj;
     __shared__ float sw[4];
     if (threadIdx.x == 0) {
-        int lo = 0, hi = njobs - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (jobs[mid].cstart <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
-        }
-        sj = lo;
+        sj = job_of_block(jobs, njobs);
     }
     __syncthreads();
     const AdamJob j = jobs[sj];
@@ -251,12 +317,7 @@ __global__ __launch_bounds__(256) void k_clip_finalize(const float* __restrict__
 __global__ __launch_bounds__(256) void k_found_inf(const AdamJob* __restrict__ jobs, int njobs, float* __restrict__ found_inf) {
     __shared__ int sj;
     if (threadIdx.x == 0) {
-        int lo = 0, hi = njobs - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (jobs[mid].cstart <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
-        }
-        sj = lo;
+        sj = job_of_block(jobs, njobs);
     }
     __syncthreads();
     const AdamJob j = jobs[sj];
@@ -388,6 +449,30 @@ int yolo_adamw_clip_step(const void* jobs_dev, int njobs, long nchunks, const do
 int yolo_amp_update_scale(float* amp_state, int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval,
                           hipStream_t st) {
     if (!(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f) || growth_interval < 1) return YOLO_ERR_ARG;
+    hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, st, amp_state, growth_tracker, growth_factor, backoff_factor, growth_interval);
+    return YOLO_LAUNCH_CHECK();
+}
+
+// ---- SGD (k_sgd) on the machinery above: the job table with v null, k_adamw_tick, the norm pass, the scale update.
+// clip_state null = unclipped; grad_scale / found_inf null = no loss scaling.
+int yolo_sgd_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale,
+                  const float* found_inf, const float* clip_state, hipStream_t st) {
+    if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
+    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, found_inf, (const AdamJob*)jobs_dev);
+    hipLaunchKernelGGL(k_sgd, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step, grad_scale,
+                       found_inf, clip_state);
+    return YOLO_LAUNCH_CHECK();
+}
+
+// yolo_adamw_amp_step's sequence around k_sgd: found_inf pass, tick, update, scale update
+int yolo_sgd_amp_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, float* amp_state,
+                      int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, hipStream_t st) {
+    if (njobs <= 0 || nchunks <= 0) return YOLO_OK;
+    if (!(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f) || growth_interval < 1) return YOLO_ERR_ARG;
+    hipLaunchKernelGGL(k_found_inf, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, amp_state + 1);
+    hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, st, step, amp_state + 1, (const AdamJob*)jobs_dev);
+    hipLaunchKernelGGL(k_sgd, dim3((unsigned)nchunks), dim3(256), 0, st, (const AdamJob*)jobs_dev, njobs, hyper, step, amp_state,
+                       amp_state + 1, (const float*)nullptr);
     hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, st, amp_state, growth_tracker, growth_factor, backoff_factor, growth_interval);
     return YOLO_LAUNCH_CHECK();
 }

@@ -31,6 +31,13 @@ from src.utils.config_loader import load_config  # noqa: E402
 WRAP = {"ddp": prepare_ddp_model, "fsdp": prepare_fsdp_model, "fsdp2": prepare_fsdp2_model}
 
 
+def optimizer_choice(tr_cfg):
+    """get_optimizer's `optimizer` / `sgd` arguments from the training section: `training.optimizer` ("adamw", the
+    reference config's value and the default, or "sgd") and the optional `training.sgd: {momentum, nesterov, warmup_steps,
+    warmup_momentum, warmup_lr_scale}`.  The reference carries the first key but never reads it."""
+    return dict(optimizer=tr_cfg.get("optimizer", "adamw"), sgd=tr_cfg.get("sgd", None))
+
+
 def main(args):
     if args.device != "cuda":
         raise SystemExit("--device cpu: this build runs the hot path on MI355X only (no CPU fallback)")
@@ -90,7 +97,7 @@ def main(args):
             raise ValueError(f"training.max_grad_norm is not supported in {args.mode} mode; use ddp mode or remove the key")
         optimizer, scheduler = get_optimizer(model=model, lr=tr_cfg["learning_rate"], weight_decay=tr_cfg["weight_decay"],
                                              patience=tr_cfg["learning_rate_patience"], factor=tr_cfg["learning_rate_factor"],
-                                             max_grad_norm=max_grad_norm)
+                                             max_grad_norm=max_grad_norm, **optimizer_choice(tr_cfg))
         # optional key `training.ema: {decay: ..., tau: ...}`: an exponential moving average of the weights kept inside the
         # optimizer step; validation runs on it and checkpoints carry it (absent = off; the reference has no EMA)
         ema = None

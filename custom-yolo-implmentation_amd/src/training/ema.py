@@ -2,7 +2,7 @@
 (`ema = d_t*ema + (1-d_t)*w` after every optimizer step, `d_t = decay*(1 - exp(-t/tau))`), kept on the device.  The
 reference has no EMA (its loop, src/training/train_model.py:247-253, validates and saves the raw weights).
 
-The average of the PARAMETERS is computed by the AdamW kernel itself (`HipAdamW(ema_decay=...)`: the kernel holds the
+The average of the PARAMETERS is computed by the optimizer kernel itself (`HipAdamW(ema_decay=...)`, `HipSGD` alike: the kernel holds the
 freshly updated parameter in a register, so the average costs one more fp32 read and write per element and no launch).
 This class adds what belongs to the model rather than to the optimizer:
 
@@ -29,9 +29,10 @@ from src.hipops.ops import _p, dt
 class ModelEMA:
     def __init__(self, model, optimizer, decay=0.9999, tau=2000.0):
         from torch.nn.parallel import DistributedDataParallel as DDP
-        from src.training.fused_adamw import HipAdamW
-        if not isinstance(optimizer, HipAdamW):
-            raise ValueError("ModelEMA (training.ema) needs HipAdamW: the average of the parameters is computed inside its step")
+        from src.training.fused_adamw import HipFusedOptimizer
+        if not isinstance(optimizer, HipFusedOptimizer):
+            raise ValueError("ModelEMA (training.ema) needs HipAdamW or HipSGD: the average of the parameters is computed "
+                             "inside their step")
         self.model = model.module if isinstance(model, DDP) else model
         self.optimizer = optimizer
         optimizer.ema_tau = tau

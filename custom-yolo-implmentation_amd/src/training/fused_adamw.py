@@ -29,6 +29,9 @@ src/training/train_model.py:247-253).
   not in the job table, so its shadow does not move on that step; the average is of the parameter AS STORED (a bf16
   parameter's rounded value).  The reference has no EMA.  Not combined with DTensor parameters.
 There is no CPU path: parameters must live on the GPU (like every op of this package).
+
+Everything above except the update rule itself lives in `HipFusedOptimizer`, the base that `HipAdamW` shares with `HipSGD`
+(src/training/fused_sgd.py; config key training.optimizer).
 """
 import torch
 
@@ -87,15 +90,20 @@ class DeviceGradScaler:
         self.growth_interval = sd["growth_interval"]
 
 
-class HipAdamW(torch.optim.Optimizer):
+class HipFusedOptimizer(torch.optim.Optimizer):
+    """What `HipAdamW` and `HipSGD` (src/training/fused_sgd.py) share: the device job table (plan / build / pointer refresh),
+    the device hyper block and step counter (`sync_hyper`), `finish_capture` / `restore_capture`, global-norm clipping
+    (`max_grad_norm`, `last_grad_norm`, `last_clip_coef`), the weight EMA (`ema_decay`, `ema_tau`, shadows, `ema_prepare`,
+    `attach_ema_buffers`), both loss-scaling routes and the DTensor rules.  A subclass names its fp32 per-parameter state
+    tensors (`_STATE`: the job record's m, then v), lays out its hyper block (`_HYPER` doubles, `_hyper_values`), may refuse a
+    group (`_check_group`) and issues its own step launches (`_step_call`, `_amp_step_call`)."""
     _step_supports_amp_scaling = True      # GradScaler hands over grad_scale / found_inf instead of unscaling itself
+    _STATE = ()
+    _HYPER = 0
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=True, max_grad_norm=None,
-                 ema_decay=None, ema_tau=2000.0):
-        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
-            raise ValueError("invalid AdamW hyper-parameter")
+    def __init__(self, params, defaults, max_grad_norm=None, ema_decay=None, ema_tau=2000.0):
         # an attribute of the optimizer, NOT a param_groups key and not in state_dict(): checkpoints stay loadable by
-        # torch.optim.AdamW and the reference
+        # the torch optimizer of the same rule and the reference
         self.max_grad_norm = max_grad_norm
         self._plans = {}                    # group index -> dict(ptrs, jobs_dev, njobs, nchunks, hyper, hyper_host, step, ema_ctl)
         self._ema = {}                      # parameter -> fp32 shadow; on the optimizer but OUTSIDE self.state (checkpoints)
@@ -103,19 +111,40 @@ class HipAdamW(torch.optim.Optimizer):
         self._ema_decay = None
         self.ema_tau = ema_tau              # the same kind of attribute as max_grad_norm: validated, not in state_dict()
         self.ema_decay = ema_decay
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                        foreach=None, capturable=True, differentiable=False, fused=True)
         super().__init__(params, defaults)
         if any(isinstance(p, DTensor) for g in self.param_groups for p in g["params"]):
             self._step_supports_amp_scaling = False     # sharded: the scaler unscales and agrees on found_inf across ranks
             if max_grad_norm is not None:
-                raise ValueError("HipAdamW: max_grad_norm is not supported with DTensor (FSDP2) parameters: the global norm "
-                                 "of sharded gradients needs a collective over the shard norms")
+                raise ValueError(f"{self._who}: max_grad_norm is not supported with DTensor (FSDP2) parameters: the global "
+                                 "norm of sharded gradients needs a collective over the shard norms")
         self._refuse_sharded_ema()
         self._clip = None                   # dict(state = fp32 [max_norm, total_norm, coef], host = uploaded max_norm, partials)
         self._pending = []                  # (jobs_dev, pinned host table) awaiting upload after a capture
         # grad_scale / found_inf are NOT pre-defined: GradScaler.step multiplies an existing grad_scale attribute in,
         # sets both around step() and deletes them afterwards
+
+    @property
+    def _who(self):
+        return type(self).__name__
+
+    # ------------------------------------------------------------------------------------------ what a subclass provides
+    def _hyper_values(self, group):
+        """The group's hyper block as a tuple of `_HYPER` floats (validated: they go to the device as they are)."""
+        raise NotImplementedError
+
+    def _check_group(self, group):
+        """Raise for a group whose keys ask for a variant the kernel does not implement."""
+
+    def _step_call(self, plan, scale, found, clip, st):
+        """Tick + update of one job table; scale / found: GradScaler protocol or None, clip: the clip state or None."""
+        raise NotImplementedError
+
+    def _amp_step_call(self, plan, amp, st):
+        """found_inf pass, tick, update and scale update of one job table under a DeviceGradScaler."""
+        raise NotImplementedError
+
+    def _plan_args(self, plan):
+        return _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]), _p(plan["step"])
 
     # ------------------------------------------------------------------------------------------ clipping
     @property
@@ -130,12 +159,12 @@ class HipAdamW(torch.optim.Optimizer):
         if value is not None:
             value = float(value)
             if not (0.0 < value <= 3.4028234664e38):        # fp32 on the device; also rejects nan
-                raise ValueError(f"HipAdamW: max_grad_norm must be finite and > 0, or None (got {value})")
+                raise ValueError(f"{self._who}: max_grad_norm must be finite and > 0, or None (got {value})")
         self._max_grad_norm = value
 
     def _clip_view(self, k):
         if self._clip is None:
-            raise RuntimeError("HipAdamW: no clipped step has run yet (max_grad_norm is None or step() was not called)")
+            raise RuntimeError(f"{self._who}: no clipped step has run yet (max_grad_norm is None or step() was not called)")
         return self._clip["state"][k]
 
     @property
@@ -153,7 +182,7 @@ class HipAdamW(torch.optim.Optimizer):
         c = self._clip
         if c is None or c["partials"].numel() < nparts or c["state"].device != dev:
             if capturing:
-                raise RuntimeError("HipAdamW: run one eager step before capturing a graph (the clip buffers are allocated there)")
+                raise RuntimeError(f"{self._who}: run one eager step before capturing a graph (the clip buffers are allocated there)")
             keep = c is not None and c["state"].device == dev      # more chunks than before: the state views stay valid
             state = c["state"] if keep else torch.tensor([self._max_grad_norm, 0.0, 1.0], dtype=torch.float32, device=dev)
             c = self._clip = dict(state=state, host=c["host"] if keep else self._max_grad_norm,
@@ -173,10 +202,10 @@ class HipAdamW(torch.optim.Optimizer):
         if value is not None:
             value = float(value)
             if not (0.0 < value < 1.0):                     # also rejects nan
-                raise ValueError(f"HipAdamW: ema_decay must lie strictly between 0 and 1, or be None (got {value})")
+                raise ValueError(f"{self._who}: ema_decay must lie strictly between 0 and 1, or be None (got {value})")
         if (value is None) != (self._ema_decay is None):
             if any(plan.get("cap_host") is not None for plan in self._plans.values()):
-                raise RuntimeError("HipAdamW: the EMA cannot be turned on or off after a graph capture (the captured job "
+                raise RuntimeError(f"{self._who}: the EMA cannot be turned on or off after a graph capture (the captured job "
                                    "tables carry the shadow pointers); capture again with a new optimizer")
             for plan in self._plans.values():
                 plan["ptrs"] = None                         # the next step rebuilds the job table with / without shadows
@@ -199,12 +228,12 @@ class HipAdamW(torch.optim.Optimizer):
     def ema_tau(self, value):
         value = float(value)
         if not (0.0 <= value <= 1.7976931348623157e308):    # also rejects nan
-            raise ValueError(f"HipAdamW: ema_tau must be finite and >= 0 (got {value})")
+            raise ValueError(f"{self._who}: ema_tau must be finite and >= 0 (got {value})")
         self._ema_tau = value
 
     def _refuse_sharded_ema(self):
         if self._ema_decay is not None and any(isinstance(p, DTensor) for g in self.param_groups for p in g["params"]):
-            raise ValueError("HipAdamW: ema_decay is not supported with DTensor (FSDP2) parameters: every rank would average "
+            raise ValueError(f"{self._who}: ema_decay is not supported with DTensor (FSDP2) parameters: every rank would average "
                              "only its shard, and nothing gathers the shadows")
 
     @property
@@ -213,7 +242,7 @@ class HipAdamW(torch.optim.Optimizer):
         update in place, like `last_grad_norm`.  Reading it syncs the host: for logging and tests only."""
         for gi in sorted(self._plans):
             return self._plans[gi]["ema_ctl"][2]
-        raise RuntimeError("HipAdamW: no step has run yet and ema_prepare() was not called")
+        raise RuntimeError(f"{self._who}: no step has run yet and ema_prepare() was not called")
 
     def ema_shadow(self, p):
         """The fp32 shadow of parameter `p`, or None (EMA off, or `p` has never been stepped nor prepared)."""
@@ -223,7 +252,7 @@ class HipAdamW(torch.optim.Optimizer):
         e = self._ema.get(p)
         if e is None:                                       # the EMA starts at the weights
             if p.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("HipAdamW: run one eager step before capturing a graph (the EMA shadows are created "
+                raise RuntimeError(f"{self._who}: run one eager step before capturing a graph (the EMA shadows are created "
                                    "there; a copy made while capturing would be replayed with every step)")
             e = self._ema[p] = _loc(p).detach().clone().to(torch.float32).contiguous()
         return e
@@ -232,7 +261,7 @@ class HipAdamW(torch.optim.Optimizer):
         """Create the control blocks and the shadow of every trainable parameter NOW instead of on its first step, so
         that `ModelEMA.load_state_dict` has something to copy into before the first step.  Needs `ema_decay`."""
         if self._ema_decay is None:
-            raise RuntimeError("HipAdamW.ema_prepare: ema_decay is None")
+            raise RuntimeError(f"{self._who}.ema_prepare: ema_decay is None")
         for gi, group in enumerate(self.param_groups):
             if group["params"]:
                 self._plan(group, gi)
@@ -242,7 +271,7 @@ class HipAdamW(torch.optim.Optimizer):
 
     def attach_ema_buffers(self, table):
         """`table` (ModelEMA's): dict(jobs_dev, njobs, nchunks) over tensors the optimizer does not step.  `step()` ends
-        with one launch over it -- after every group's AdamW launch, so the update count already includes the step."""
+        with one launch over it -- after every group's step launch, so the update count already includes the step."""
         self._ema_buffers = table
 
     # ------------------------------------------------------------------------------------------ state
@@ -251,7 +280,7 @@ class HipAdamW(torch.optim.Optimizer):
         if plan is None:
             dev = next(p.device for p in group["params"])
             plan = self._plans[gi] = dict(ptrs=None, jobs_dev=None, host=None, njobs=0, nchunks=0, hyper_host=None,
-                                          hyper=torch.zeros(5, dtype=torch.float64, device=dev),
+                                          hyper=torch.zeros(self._HYPER, dtype=torch.float64, device=dev),
                                           step=torch.zeros((), dtype=torch.float32, device=dev),
                                           ema_ctl=torch.zeros(3, dtype=torch.float64, device=dev), ema_host=None)
         return plan
@@ -262,20 +291,25 @@ class HipAdamW(torch.optim.Optimizer):
             if self._ema_decay is not None and _grad(p) is not None:
                 self._shadow(p)
             st = self.state[p]
-            if "exp_avg" not in st:
+            if self._STATE[0] not in st:
                 st["step"] = plan["step"]                           # one shared device counter per group
-                if isinstance(p, DTensor):                           # same mesh / placement as the parameter
-                    st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
-                    st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
-                else:
-                    st["exp_avg"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
-                    st["exp_avg_sq"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
-            elif st["step"] is not plan["step"]:                    # after load_state_dict: adopt the loaded count
-                plan["step"].copy_(torch.as_tensor(st["step"], dtype=torch.float32).reshape(()))
+                for name in self._STATE:
+                    st[name] = self._zeros(p)
+            elif st.get("step") is not plan["step"]:
+                # after load_state_dict: adopt the loaded count (a torch optimizer that keeps none: 0) and tensors (one
+                # that torch left unset: zeros); the job table is rebuilt, because it points at the tensors they replace
+                plan["step"].copy_(torch.as_tensor(st.get("step", 0.0), dtype=torch.float32).reshape(()))
                 st["step"] = plan["step"]
-                st["exp_avg"] = st["exp_avg"].to(torch.float32)
-                st["exp_avg_sq"] = st["exp_avg_sq"].to(torch.float32)
+                for name in self._STATE:
+                    st[name] = self._zeros(p) if st.get(name) is None else st[name].to(torch.float32)
+                plan["ptrs"] = None
         return plan
+
+    @staticmethod
+    def _zeros(p):
+        if isinstance(p, DTensor):                                  # same mesh / placement as the parameter
+            return torch.zeros_like(p, dtype=torch.float32)
+        return torch.zeros(p.shape, dtype=torch.float32, device=p.device)
 
     def sync_hyper(self):
         """Copy changed hyper-parameters (e.g. a scheduler's new lr) to the device; call between graph replays."""
@@ -283,8 +317,7 @@ class HipAdamW(torch.optim.Optimizer):
             plan = self._plans.get(gi)
             if plan is None:
                 continue
-            want = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
-                    float(group["weight_decay"]))
+            want = self._hyper_values(group)
             if plan["hyper_host"] != want:
                 plan["hyper"].copy_(torch.tensor(want, dtype=torch.float64))
                 plan["hyper_host"] = want
@@ -319,9 +352,10 @@ class HipAdamW(torch.optim.Optimizer):
     # ------------------------------------------------------------------------------------------ step
     @torch.no_grad()
     def step(self, closure=None):
-        """One launch for all parameters of a group.  Deviation from torch.optim.AdamW: the step counter (bias correction)
-        is per GROUP, not per parameter -- a parameter that receives no gradient on some steps is corrected as if it had
-        been stepped with the others (the reference's model gives every parameter a gradient on every step).  The EMA
+        """One launch for all parameters of a group.  Deviation from torch.optim.AdamW / SGD: the step counter (AdamW's bias
+        correction, SGD's warm-up position) is per GROUP, not per parameter -- a parameter that receives no gradient on some
+        steps is corrected as if it had been stepped with the others (the reference's model gives every parameter a
+        gradient on every step).  The EMA
         (`ema_decay`) shares that table: the update count is per group too, and a parameter without a gradient on a step
         is not in the table, so its shadow does not move on that step."""
         loss = None
@@ -333,8 +367,7 @@ class HipAdamW(torch.optim.Optimizer):
             params = [p for p in group["params"] if _grad(p) is not None]
             if not params:
                 continue
-            if group.get("amsgrad") or group.get("maximize"):
-                raise RuntimeError("HipAdamW implements plain AdamW (amsgrad=False, maximize=False)")
+            self._check_group(group)
             plan = self._init_state(group, gi)
             capturing = torch.cuda.is_current_stream_capturing()
             ptrs = tuple((_loc(p).data_ptr(), _loc(_grad(p)).data_ptr(), _loc(p).numel()) for p in params)
@@ -367,7 +400,7 @@ class HipAdamW(torch.optim.Optimizer):
             if not capturing:
                 self.sync_hyper()
             elif plan["hyper_host"] is None:
-                raise RuntimeError("HipAdamW: run one eager step (or sync_hyper()) before capturing a graph")
+                raise RuntimeError(f"{self._who}: run one eager step (or sync_hyper()) before capturing a graph")
             if ema_ctl is None:
                 ema_ctl, ema_on = plan["ema_ctl"], params[0]
             if self._max_grad_norm is not None:
@@ -391,16 +424,14 @@ class HipAdamW(torch.optim.Optimizer):
     def _launch(self, plan, params):
         amp = getattr(self, "device_amp", None)
         if amp is not None:     # fp16 loss scaling kept on the device (DeviceGradScaler): found_inf, step, scale update
-            lib.call("yolo_adamw_amp_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
-                     _p(plan["step"]), _p(amp.state), _p(amp.tracker), float(amp.growth_factor), float(amp.backoff_factor),
-                     int(amp.growth_interval), _stream(_loc(params[0])))
+            self._amp_step_call(plan, amp, _stream(_loc(params[0])))
             return
-        lib.call("yolo_adamw_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
-                 _p(plan["step"]), _p(getattr(self, "grad_scale", None)), _p(getattr(self, "found_inf", None)),
-                 _stream(_loc(params[0])))      # GradScaler sets the two attributes around step() and deletes them after
+        # GradScaler sets the two attributes around step() and deletes them after
+        self._step_call(plan, getattr(self, "grad_scale", None), getattr(self, "found_inf", None), None,
+                        _stream(_loc(params[0])))
 
     def _clipped_step(self, ready):
-        """Norm pass of every group into ONE partials buffer, one finalize, then the AdamW launches with the clip state.
+        """Norm pass of every group into ONE partials buffer, one finalize, then the step launches with the clip state.
         With `device_amp` the norm pass also raises found_inf (it replaces the separate found_inf pass) and the scale
         update follows the last group; with GradScaler's grad_scale attribute the norm is that of the unscaled gradients."""
         dev = ready[0][1][0].device
@@ -422,8 +453,7 @@ class HipAdamW(torch.optim.Optimizer):
             off += plan["nchunks"]
         lib.call("yolo_grad_clip_finalize", _p(clip["partials"]), nparts, _p(clip["state"]), _p(scale), st)
         for plan, _ in ready:
-            lib.call("yolo_adamw_clip_step", _p(plan["jobs_dev"]), plan["njobs"], plan["nchunks"], _p(plan["hyper"]),
-                     _p(plan["step"]), _p(scale), _p(found), _p(clip["state"]), st)
+            self._step_call(plan, scale, found, clip["state"], st)
         if amp is not None:
             lib.call("yolo_amp_update_scale", _p(amp.state), _p(amp.tracker), float(amp.growth_factor),
                      float(amp.backoff_factor), int(amp.growth_interval), st)
@@ -433,23 +463,25 @@ class HipAdamW(torch.optim.Optimizer):
         n = len(params)
         if plan["host"] is None or plan["host"].numel() != n * jb:
             if capturing:
-                raise RuntimeError("HipAdamW: run one eager step before capturing a graph (host/device tables are "
+                raise RuntimeError(f"{self._who}: run one eager step before capturing a graph (host/device tables are "
                                    "allocated there)")
             plan["host"] = torch.zeros(n * jb, dtype=torch.uint8).pin_memory()
             plan["jobs_dev"] = torch.empty(n * jb, dtype=torch.uint8, device=_loc(params[0]).device)
         host = plan["host"]
         for i, p in enumerate(params):
             st = self.state[p]
-            w, g, m1, m2 = _loc(p), _loc(_grad(p)), _loc(st["exp_avg"]), _loc(st["exp_avg_sq"])
-            if not (w.is_contiguous() and g.is_contiguous() and m1.is_contiguous() and m2.is_contiguous()):
-                raise RuntimeError("HipAdamW needs contiguous parameters, gradients and moments")
-            if not (g.numel() == m1.numel() == m2.numel() == w.numel()):
-                raise RuntimeError("HipAdamW: gradient / moment shards do not match the parameter's local shard")
-            lib.call("yolo_adamw_job_fill", host.data_ptr(), i, _p(w), dt(w), _p(g), dt(g), _p(m1), _p(m2), w.numel())
+            w, g = _loc(p), _loc(_grad(p))
+            bufs = [_loc(st[name]) for name in self._STATE]
+            if not (w.is_contiguous() and g.is_contiguous() and all(b.is_contiguous() for b in bufs)):
+                raise RuntimeError(f"{self._who} needs contiguous parameters, gradients and state tensors")
+            if g.numel() != w.numel() or any(b.numel() != w.numel() for b in bufs):
+                raise RuntimeError(f"{self._who}: gradient / state shards do not match the parameter's local shard")
+            lib.call("yolo_adamw_job_fill", host.data_ptr(), i, _p(w), dt(w), _p(g), dt(g), _p(bufs[0]),
+                     _p(bufs[1]) if len(bufs) > 1 else 0, w.numel())
             if self._ema_decay is not None:
                 e = self._ema[p]
                 if e.numel() != w.numel() or e.device != w.device:
-                    raise RuntimeError("HipAdamW: an EMA shadow does not match its parameter's local shard")
+                    raise RuntimeError(f"{self._who}: an EMA shadow does not match its parameter's local shard")
                 lib.call("yolo_adamw_job_set_ema", host.data_ptr(), i, _p(e), _p(plan["ema_ctl"]))
         plan["nchunks"] = lib.query("yolo_adamw_jobs_finalize", host.data_ptr(), n)
         plan["njobs"] = n
@@ -459,3 +491,34 @@ class HipAdamW(torch.optim.Optimizer):
             self._pending.append((plan["jobs_dev"], host))
         else:
             plan["jobs_dev"].copy_(host)
+
+
+class HipAdamW(HipFusedOptimizer):
+    _STATE = ("exp_avg", "exp_avg_sq")
+    _HYPER = 5                              # [lr, beta1, beta2, eps, weight_decay]
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=True, max_grad_norm=None,
+                 ema_decay=None, ema_tau=2000.0):
+        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("invalid AdamW hyper-parameter")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=None, capturable=True, differentiable=False, fused=True)
+        super().__init__(params, defaults, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_tau=ema_tau)
+
+    def _hyper_values(self, group):
+        return (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
+                float(group["weight_decay"]))
+
+    def _check_group(self, group):
+        if group.get("amsgrad") or group.get("maximize"):
+            raise RuntimeError("HipAdamW implements plain AdamW (amsgrad=False, maximize=False)")
+
+    def _step_call(self, plan, scale, found, clip, st):
+        if clip is None:
+            lib.call("yolo_adamw_step", *self._plan_args(plan), _p(scale), _p(found), st)
+        else:
+            lib.call("yolo_adamw_clip_step", *self._plan_args(plan), _p(scale), _p(found), _p(clip), st)
+
+    def _amp_step_call(self, plan, amp, st):
+        lib.call("yolo_adamw_amp_step", *self._plan_args(plan), _p(amp.state), _p(amp.tracker), float(amp.growth_factor),
+                 float(amp.backoff_factor), int(amp.growth_interval), st)

@@ -147,10 +147,10 @@ class TrainStepRunner:
         # fp16: dynamic loss scaling kept on the device (no GradScaler round trips: the step stays capturable)
         self.amp = None
         if precision == "float16":
-            from src.training.fused_adamw import DeviceGradScaler, HipAdamW
-            if not isinstance(optimizer, HipAdamW) or len(optimizer.param_groups) != 1:
-                raise RuntimeError("TrainStepRunner(precision='float16') needs HipAdamW with one parameter group: the loss "
-                                   "scale, the overflow check and the skipped / unscaled update run on the device")
+            from src.training.fused_adamw import DeviceGradScaler, HipFusedOptimizer
+            if not isinstance(optimizer, HipFusedOptimizer) or len(optimizer.param_groups) != 1:
+                raise RuntimeError("TrainStepRunner(precision='float16') needs HipAdamW or HipSGD with one parameter group: "
+                                   "the loss scale, the overflow check and the skipped / unscaled update run on the device")
             self.amp = getattr(optimizer, "device_amp", None) or DeviceGradScaler(self.params[0].device)
             optimizer.device_amp = self.amp
         self.graph = None

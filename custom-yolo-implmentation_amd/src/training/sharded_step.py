@@ -119,19 +119,21 @@ class ShardState:
         return out
 
     def full_optimizer_state_dict(self, optimizer):
-        """The sharded AdamW state as the state dict of a torch.optim.AdamW over the bare model's trainable parameters (in
-        `model.parameters()` order): moments gathered from every rank (a collective) and cut per parameter."""
+        """The sharded optimizer state as the state dict of a torch.optim.AdamW (HipSGD: torch.optim.SGD) over the bare
+        model's trainable parameters (in `model.parameters()` order): moments gathered from every rank (a collective) and
+        cut per parameter."""
         st = optimizer.state.get(self.master, {})
         sd = optimizer.state_dict()
         group = dict(sd["param_groups"][0])
         group["params"] = list(range(len(self.trainable)))
         state = {}
-        if "exp_avg" in st:
-            m1, m2 = self.gather_flat(st["exp_avg"]), self.gather_flat(st["exp_avg_sq"])
+        names = getattr(optimizer, "_STATE", ("exp_avg", "exp_avg_sq"))      # HipSGD: ("momentum_buffer",)
+        if names[0] in st:
+            flats = [self.gather_flat(st[name]) for name in names]
             step = torch.as_tensor(st["step"]).detach().float().cpu().reshape(())
             for i, (p, (o, n)) in enumerate(zip(self.trainable, self.slices)):
-                state[i] = dict(step=step.clone(), exp_avg=m1[o:o + n].view(p.shape).cpu().clone(),
-                                exp_avg_sq=m2[o:o + n].view(p.shape).cpu().clone())
+                state[i] = dict(step=step.clone(), **{name: f[o:o + n].view(p.shape).cpu().clone()
+                                                      for name, f in zip(names, flats)})
         return dict(state=state, param_groups=[group])
 
 

@@ -77,7 +77,7 @@ class CapturedTraining:
     group): all ranks replay or all ranks step eagerly, with the same buckets and reduction either way.  Needs a
     capturable optimizer.  float16: no torch GradScaler on this route -- the loss scale, the overflow check, the skipped or
     unscaled update and the scale's growth / backoff (GradScaler's rules and defaults, reference :195-208,247-253) run on the
-    device inside the captured step (`DeviceGradScaler`, needs `HipAdamW`)."""
+    device inside the captured step (`DeviceGradScaler`, needs `HipAdamW` or `HipSGD`)."""
 
     def __init__(self, model, criterion, optimizer, precision, grad_compress=None, ema=None):
         import torch.distributed as dist
@@ -94,11 +94,11 @@ class CapturedTraining:
         self.flag_group = None
         # (a wrapper built elsewhere on the default stream cannot be captured -- see prepare_ddp_model; TrainStepRunner.capture
         # measures that on its warm-up step and keeps stepping eagerly then: no flag to trust)
-        from src.training.fused_adamw import HipAdamW
+        from src.training.fused_adamw import HipFusedOptimizer
         self.usable = precision in ("bfloat16", "float32", "float16") and \
             all(g.get("capturable", False) for g in optimizer.param_groups) and \
             all(type(p) is torch.nn.Parameter and p.is_cuda for p in self.inner.parameters()) and \
-            (precision != "float16" or (isinstance(optimizer, HipAdamW) and len(optimizer.param_groups) == 1))
+            (precision != "float16" or (isinstance(optimizer, HipFusedOptimizer) and len(optimizer.param_groups) == 1))
 
     def _all_fit(self, fits):
         """AND of the ranks' `fits` flags (host side: no device sync)."""
@@ -263,10 +263,10 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
         if distributed_mode in ("fsdp", "fsdp2") or getattr(model, "_native_shard", None) is not None:
             raise ValueError(f"training.ema is not supported in {distributed_mode} mode: the shadows of sharded parameters "
                              "would be shards that nothing gathers; use ddp mode or remove the key")
-        from src.training.fused_adamw import HipAdamW
-        if not isinstance(optimizer, HipAdamW) or optimizer.ema_decay is None:
-            raise ValueError("training.ema is set but the optimizer keeps no average: it needs a HipAdamW with ema_decay set "
-                             "(build a ModelEMA over the optimizer that get_optimizer returns)")
+        from src.training.fused_adamw import HipFusedOptimizer
+        if not isinstance(optimizer, HipFusedOptimizer) or optimizer.ema_decay is None:
+            raise ValueError("training.ema is set but the optimizer keeps no average: it needs a HipAdamW or HipSGD with "
+                             "ema_decay set (build a ModelEMA over the optimizer that get_optimizer returns)")
     if max_grad_norm is None:
         max_grad_norm = getattr(optimizer, "max_grad_norm", None)
     if max_grad_norm is not None:

@@ -22,8 +22,12 @@ from src.utils.common import get_num_threads
 _LOWP = ("bfloat16", "float16")
 
 
+_SGD_KEYS = ("momentum", "nesterov", "warmup_steps", "warmup_momentum", "warmup_lr_scale")
+
+
 def get_optimizer(model: nn.Module, lr: float, weight_decay: float, patience: int, factor: float,
-                  max_grad_norm: float = None) -> Tuple[optim.Optimizer, optim.lr_scheduler.ReduceLROnPlateau]:
+                  max_grad_norm: float = None, optimizer: str = "adamw",
+                  sgd: dict = None) -> Tuple[optim.Optimizer, optim.lr_scheduler.ReduceLROnPlateau]:
     """AdamW + ReduceLROnPlateau (reference :20-36).  GPU parameters get the one-launch `HipAdamW` (same update rule,
     state names and scheduler / GradScaler / checkpoint behaviour as torch.optim.AdamW, whose default eager form issues
     several small kernels per parameter): plain parameters (single GPU, DDP) and FSDP2's DTensor parameters, whose local
@@ -31,8 +35,28 @@ def get_optimizer(model: nn.Module, lr: float, weight_decay: float, patience: in
     flat shards, re-pointed every step: it keeps torch.optim.AdamW, and so does anything on the CPU.
     `max_grad_norm` (optional config key training.max_grad_norm; None = off): global-norm gradient clipping inside
     HipAdamW's step.  Only plain GPU parameters have it: the sharded routes and torch.optim.AdamW raise a ValueError
-    instead of training unclipped."""
+    instead of training unclipped.
+    `optimizer` (config key training.optimizer, which the reference carries at config.yaml:65 but never reads; any letter
+    case): "adamw" = all of the above; "sgd" = SGD with Nesterov momentum, `HipSGD` wherever HipAdamW would be built (the
+    native master shard included: the update is element-wise) and torch.optim.SGD where torch.optim.AdamW is the fallback.
+    `sgd` (optional config key training.sgd, ignored unless the optimizer is "sgd"; unknown keys raise either way):
+    {momentum, nesterov, warmup_steps, warmup_momentum, warmup_lr_scale}; torch's
+    SGD has no warm-up, so there warmup_steps > 0 raises, like max_grad_norm.  Any other name raises: a config that names an
+    optimizer this package does not have must not silently train AdamW."""
     from torch.distributed.tensor import DTensor
+    name = str(optimizer).lower()
+    if name not in ("adamw", "sgd"):
+        raise ValueError(f"training.optimizer: expected 'adamw' or 'sgd', got {optimizer!r}")
+    sgd = dict(sgd or {})                   # read with "sgd" only: a config switched back to "adamw" may keep the section
+    unknown = sorted(set(sgd) - set(_SGD_KEYS))
+    if unknown:
+        raise ValueError(f"training.sgd: unknown keys {unknown}; expected some of {list(_SGD_KEYS)}")
+    if name == "sgd":
+        from src.training.fused_sgd import HipSGD
+        fused = lambda ps, **kw: HipSGD(ps, lr=lr, weight_decay=weight_decay, **sgd, **kw)
+    else:
+        from src.training.fused_adamw import HipAdamW
+        fused = lambda ps, **kw: HipAdamW(ps, lr=lr, weight_decay=weight_decay, **kw)
     native = getattr(model, "_native_shard", None)
     if native is not None:
         if max_grad_norm is not None:
@@ -40,22 +64,26 @@ def get_optimizer(model: nn.Module, lr: float, weight_decay: float, patience: in
                              "gradients needs a collective over the shard norms")
         # `prepare_fsdp2_model(native_shard: true)`: the model is sharded HERE (flat low-precision parameters, this rank's
         # fp32 master shard) and the optimizer steps the master shard; train() drives both through ShardedStepRunner
-        from src.training.fused_adamw import HipAdamW
         from src.training.sharded_step import ShardState
         if native.get("state") is None:
             native["state"] = ShardState(model, native["precision"])
-        opt = HipAdamW([native["state"].master], lr=lr, weight_decay=weight_decay)
+        opt = fused([native["state"].master])
         native["optimizer"] = opt
         return opt, optim.lr_scheduler.ReduceLROnPlateau(opt, patience=patience, factor=factor)
     params = list(model.parameters())
     fsdp1 = isinstance(model, FSDP) or any(isinstance(m, FSDP) for m in model.modules())
     ok = lambda p: (type(p) is nn.Parameter and p.is_cuda) or (isinstance(p, DTensor) and p._local_tensor.is_cuda)
     if params and not fsdp1 and all(ok(p) for p in params):
-        from src.training.fused_adamw import HipAdamW
-        opt = HipAdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        opt = fused(params, max_grad_norm=max_grad_norm)
     elif max_grad_norm is not None:
-        raise ValueError("training.max_grad_norm needs HipAdamW (plain parameters on the GPU: single GPU or ddp mode); "
-                         "FSDP1 and CPU parameters step through torch.optim.AdamW, which does not clip")
+        raise ValueError("training.max_grad_norm needs HipAdamW or HipSGD (plain parameters on the GPU: single GPU or ddp "
+                         "mode); FSDP1 and CPU parameters step through torch.optim.AdamW / SGD, which do not clip")
+    elif name == "sgd":
+        if int(sgd.get("warmup_steps", 0)) > 0:
+            raise ValueError("training.sgd.warmup_steps needs HipSGD (plain parameters on the GPU: single GPU or ddp mode); "
+                             "FSDP1 and CPU parameters step through torch.optim.SGD, which has no warm-up")
+        opt = optim.SGD(params, lr=lr, weight_decay=weight_decay, momentum=sgd.get("momentum", 0.937),
+                        nesterov=sgd.get("nesterov", True))
     else:
         opt = optim.AdamW(params, lr=lr, weight_decay=weight_decay)
     return opt, optim.lr_scheduler.ReduceLROnPlateau(opt, patience=patience, factor=factor)
@@ -154,18 +182,18 @@ def load_checkpoint(model: nn.Module, optimizer: optim.Optimizer, path: str, map
                 st.flat_p.copy_(full.to(st.flat_p.dtype))
             if optimizer is not None and isinstance(ck, dict) and ck.get("optimizer_state", {}).get("state"):
                 os_ = ck["optimizer_state"]["state"]
-                m1 = torch.zeros(st.total, dtype=torch.float32, device=st.master.device)
-                m2 = torch.zeros_like(m1)
+                names = getattr(optimizer, "_STATE", ("exp_avg", "exp_avg_sq"))      # HipSGD: ("momentum_buffer",)
+                flats = {k: torch.zeros(st.total, dtype=torch.float32, device=st.master.device) for k in names}
                 for i, (q, (o, n)) in enumerate(zip(st.trainable, st.slices)):
                     e = os_.get(i, os_.get(str(i)))
                     if e is not None:
-                        m1[o:o + n].copy_(e["exp_avg"].reshape(-1).float())
-                        m2[o:o + n].copy_(e["exp_avg_sq"].reshape(-1).float())
-                step = float(next(iter(os_.values()))["step"])
+                        for k in names:
+                            if e.get(k) is not None:                 # torch.optim.SGD leaves an unset buffer as None: zeros
+                                flats[k][o:o + n].copy_(e[k].reshape(-1).float())
+                step = float(next(iter(os_.values())).get("step", 0.0))     # torch.optim.SGD keeps no count: 0
                 lo = st.rank * st.shard_elems
                 optimizer.load_state_dict(dict(
-                    state={0: dict(step=torch.tensor(step), exp_avg=m1[lo:lo + st.shard_elems].clone(),
-                                   exp_avg_sq=m2[lo:lo + st.shard_elems].clone())},
+                    state={0: dict(step=torch.tensor(step), **{k: f[lo:lo + st.shard_elems].clone() for k, f in flats.items()})},
                     param_groups=[dict(ck["optimizer_state"]["param_groups"][0], params=[0])]))
         return int(ck["epoch"]) if isinstance(ck, dict) and "epoch" in ck else 0
     if _is_sharded(model):

@@ -101,6 +101,17 @@ int yolo_grad_sqnorm(const void* jobs_dev, int njobs, long nchunks, float* parti
 int yolo_grad_clip_finalize(const float* partials, long nparts, float* clip_state, const float* grad_scale, hipStream_t st);
 int yolo_adamw_clip_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale, const float* found_inf, const float* clip_state, hipStream_t st);
 int yolo_amp_update_scale(float* amp_state, int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, hipStream_t st);
+/* ---- SGD optimizer: torch.optim.SGD(momentum, dampening 0, coupled weight_decay, nesterov, maximize False) over all parameters
+   in one launch, chosen by the config key training.optimizer (reference: config.yaml:65 carries the key, but
+   src/training/utils_train.py:34 get_optimizer never reads it and always builds AdamW; step at src/training/train_model.py:247-253).
+   The job table, step counter, EMA records, grad_scale / found_inf, clip_state and amp_state are the AdamW block's (records
+   filled with v null, m = the momentum buffer); yolo_grad_sqnorm, yolo_grad_clip_finalize, yolo_amp_update_scale and
+   yolo_ema_lerp serve both.  hyper = device doubles [lr, momentum, weight_decay, nesterov (0 / 1), warmup_steps W,
+   warmup_momentum mu0, warmup_lr_scale s0]: with t = step after this call's increment and f = (t-1)/W, a step with t <= W
+   runs at lr*(s0 + (1-s0)*f) and mu0 + (momentum-mu0)*f, later steps (and W = 0) at lr and momentum; a step skipped on
+   found_inf advances neither.  clip_state null = unclipped.  yolo_sgd_amp_step: found_inf pass, step, scale update. */
+int yolo_sgd_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, const float* grad_scale, const float* found_inf, const float* clip_state, hipStream_t st);
+int yolo_sgd_amp_step(const void* jobs_dev, int njobs, long nchunks, const double* hyper, float* step, float* amp_state, int* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, hipStream_t st);
 /* ---- gradient exchange: pack / unpack every parameter gradient into / out of the flat communication buffers in one launch
    (DistributedDataParallel's bucket copies: src/training/utils_train.py:190); jobs: device copy of a host table of
    yolo_copy_job_bytes() records, dst = src * scale with a dtype cast */
