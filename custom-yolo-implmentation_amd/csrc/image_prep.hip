@@ -14,6 +14,8 @@
 //   to float      x / 255, (x - mean) / std
 // Stages: resize+flip -> uint8 planar staging; per jitter slot k = 0..3 a per-image gray-mean reduction and the op that
 // image has in slot k; the last launch converts, normalises and writes NCHW in the model's input dtype.
+// Mosaic (no reference counterpart; opt-in): k_mosaic takes the place of the resize launch and composes each output from
+// four resized tiles of the batch's own images around a centre, fill elsewhere; the colour chain behind it is the same.
 #include "common.h"
 
 struct PrepImage {
@@ -22,6 +24,17 @@ struct PrepImage {
     int flip;
     int order[4];       // op in jitter slot k: 0 brightness, 1 contrast, 2 saturation, 3 hue, -1 none
     float factor[4];    // factor of op o (indexed by op, not by slot)
+};
+
+// one of the four tiles of a mosaic output (tile k touches the centre (cx, cy) with one corner: 0 top-left, 1 top-right,
+// 2 bottom-left, 3 bottom-right): the source image resized to (th, tw) and placed with its top-left corner at (x0, y0)
+struct MosaicTile {
+    long off;           // byte offset of the source image in the source buffer
+    int H, W;
+    int flip;
+    int tw, th;         // size of the resized tile; 0 = no tile (the quadrant is fill)
+    int x0, y0;         // canvas position of the tile's pixel (0, 0); may be negative (the quadrant clips the tile)
+    int cx, cy;         // the output's centre, repeated in its four tiles
 };
 
 namespace {
@@ -41,27 +54,25 @@ __device__ __forceinline__ Taps taps_of(int i, int in_size, int out_size) {
     return t;
 }
 
-// one thread per output pixel: all three channels
-__global__ __launch_bounds__(256) void k_resize_flip(const unsigned char* __restrict__ src, const PrepImage* __restrict__ imgs,
-                                                    unsigned char* __restrict__ stage, int S) {
-    const int n = blockIdx.z;
-    const PrepImage im = imgs[n];
-    const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-    if (ox >= S) return;
-    const Taps ty = taps_of(oy, im.H, S), tx = taps_of(ox, im.W, S);
+// output pixel (oy, ox) of the image at `base` (uint8 HWC, H x W, optionally mirrored) resized to (out_h, out_w): all three
+// channels, rounded to uint8 levels.  The one pixel routine of k_resize_flip and k_mosaic: the same operations in the same
+// order for both (this file is compiled without floating-point contraction), so a mosaic record that describes a plain
+// resize reproduces k_resize_flip bit for bit.  Reads stay inside [0, H) x [0, W) by the clamping in taps_of.
+__device__ __forceinline__ void resize_pixel(const unsigned char* __restrict__ base, int H, int W, int flip, int oy, int ox,
+                                             int out_h, int out_w, unsigned char px[3]) {
+    const Taps ty = taps_of(oy, H, out_h), tx = taps_of(ox, W, out_w);
     float wsum_y = 0.f, wsum_x = 0.f;
     for (int j = 0; j < ty.n; ++j) wsum_y += tri(((float)(j + ty.lo) - ty.center + 0.5f) * ty.inv);
     for (int j = 0; j < tx.n; ++j) wsum_x += tri(((float)(j + tx.lo) - tx.center + 0.5f) * tx.inv);
     float acc[3] = {0.f, 0.f, 0.f};
-    const unsigned char* base = src + im.off;
     for (int jy = 0; jy < ty.n; ++jy) {
         const float wy = tri(((float)(jy + ty.lo) - ty.center + 0.5f) * ty.inv) / wsum_y;
-        const unsigned char* row = base + (long)(ty.lo + jy) * im.W * 3;
+        const unsigned char* row = base + (long)(ty.lo + jy) * W * 3;
         float r[3] = {0.f, 0.f, 0.f};
         for (int jx = 0; jx < tx.n; ++jx) {
             const float wx = tri(((float)(jx + tx.lo) - tx.center + 0.5f) * tx.inv);
             const int sx = tx.lo + jx;
-            const unsigned char* p = row + (long)(im.flip ? im.W - 1 - sx : sx) * 3;
+            const unsigned char* p = row + (long)(flip ? W - 1 - sx : sx) * 3;
             r[0] += wx * (float)p[0]; r[1] += wx * (float)p[1]; r[2] += wx * (float)p[2];
         }
 #pragma unroll
@@ -70,8 +81,38 @@ __global__ __launch_bounds__(256) void k_resize_flip(const unsigned char* __rest
     // a flipped image is resized from the flipped source: output column ox reads mirrored columns, i.e. the same
     // result as flipping first (the filter is symmetric); written at ox
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-        stage[(((long)n * 3 + c) * S + oy) * S + ox] = (unsigned char)fminf(fmaxf(floorf(acc[c] + 0.5f), 0.f), 255.f);
+    for (int c = 0; c < 3; ++c) px[c] = (unsigned char)fminf(fmaxf(floorf(acc[c] + 0.5f), 0.f), 255.f);
+}
+
+// one thread per output pixel: all three channels
+__global__ __launch_bounds__(256) void k_resize_flip(const unsigned char* __restrict__ src, const PrepImage* __restrict__ imgs,
+                                                    unsigned char* __restrict__ stage, int S) {
+    const int n = blockIdx.z;
+    const PrepImage im = imgs[n];
+    const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (ox >= S) return;
+    unsigned char px[3];
+    resize_pixel(src + im.off, im.H, im.W, im.flip, oy, ox, S, S, px);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) stage[(((long)n * 3 + c) * S + oy) * S + ox] = px[c];
+}
+
+// mosaic: one thread per canvas pixel, four tile records per output image.  The pixel belongs to the quadrant its side of
+// the centre says; inside that quadrant's tile rectangle it is the tile's resized pixel, elsewhere the fill level (no
+// taps are computed there).  A tile with tw = 0 (an unreachable quadrant of a plain record) is never sampled.
+__global__ __launch_bounds__(256) void k_mosaic(const unsigned char* __restrict__ src, const MosaicTile* __restrict__ tiles,
+                                               unsigned char* __restrict__ stage, int S, int fill) {
+    const int n = blockIdx.z;
+    const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (ox >= S) return;
+    const MosaicTile* quad = tiles + (long)n * 4;
+    const int k = (ox >= quad[0].cx ? 1 : 0) + (oy >= quad[0].cy ? 2 : 0);
+    const MosaicTile t = quad[k];
+    const int lx = ox - t.x0, ly = oy - t.y0;
+    unsigned char px[3] = {(unsigned char)fill, (unsigned char)fill, (unsigned char)fill};
+    if (lx >= 0 && lx < t.tw && ly >= 0 && ly < t.th) resize_pixel(src + t.off, t.H, t.W, t.flip, ly, lx, t.th, t.tw, px);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) stage[(((long)n * 3 + c) * S + oy) * S + ox] = px[c];
 }
 
 __device__ __forceinline__ float gray_of(float r, float g, float b) { return floorf(0.2989f * r + 0.587f * g + 0.114f * b); }
@@ -173,14 +214,24 @@ int yolo_prep_image_fill(void* table_host, int index, long off, int H, int W, in
     return YOLO_OK;
 }
 
-// src: all images of the batch, uint8 HWC, back to back (table[i].off); stage: uint8 scratch [N][3][S][S]; means: fp32
-// scratch [4][N]; out: [N][3][S][S] of out_dtype.  jitter = 0 skips the colour stages (validation transform).
-int yolo_image_prep(const void* src, const void* table_dev, int N, int S, int jitter, void* stage, float* means, void* out,
-                    int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
-    if (N <= 0 || S <= 0) return YOLO_ERR_ARG;
-    const PrepImage* imgs = (const PrepImage*)table_dev;
-    hipLaunchKernelGGL(k_resize_flip, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src, imgs,
-                       (unsigned char*)stage, S);
+int yolo_mosaic_tile_bytes(void) { return (int)sizeof(MosaicTile); }
+
+// fill tile `tile` (0..3) of output `image` in the host-side tile table ([N][4] records, zeroed by the caller: a tile left
+// zeroed is all fill)
+int yolo_mosaic_tile_fill(void* table_host, int image, int tile, long off, int H, int W, int flip, int tw, int th, int x0, int y0,
+                          int cx, int cy) {
+    if (H <= 0 || W <= 0 || tw <= 0 || th <= 0 || tile < 0 || tile > 3 || image < 0) return YOLO_ERR_ARG;
+    MosaicTile& t = ((MosaicTile*)table_host)[(long)image * 4 + tile];
+    t.off = off; t.H = H; t.W = W; t.flip = flip; t.tw = tw; t.th = th; t.x0 = x0; t.y0 = y0; t.cx = cx; t.cy = cy;
+    return YOLO_OK;
+}
+
+}  // extern "C"
+
+// the colour chain on the staging buffer: per jitter slot a gray-mean reduction and that slot's op, the last launch
+// converts, normalises and writes NCHW (jitter = 0: that last launch alone)
+static int color_chain(const PrepImage* imgs, int N, int S, int jitter, void* stage, float* means, void* out, int out_dtype,
+                       float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
     const long hw = (long)S * S;
     int gx = (int)((hw + 255) / 256);
     if (gx > 64) gx = 64;
@@ -202,6 +253,30 @@ int yolo_image_prep(const void* src, const void* table_dev, int N, int S, int ji
         }
     }
     return YOLO_LAUNCH_CHECK();
+}
+
+extern "C" {
+
+// src: all images of the batch, uint8 HWC, back to back (table[i].off); stage: uint8 scratch [N][3][S][S]; means: fp32
+// scratch [4][N]; out: [N][3][S][S] of out_dtype.  jitter = 0 skips the colour stages (validation transform).
+int yolo_image_prep(const void* src, const void* table_dev, int N, int S, int jitter, void* stage, float* means, void* out,
+                    int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
+    if (N <= 0 || S <= 0) return YOLO_ERR_ARG;
+    const PrepImage* imgs = (const PrepImage*)table_dev;
+    hipLaunchKernelGGL(k_resize_flip, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src, imgs,
+                       (unsigned char*)stage, S);
+    return color_chain(imgs, N, S, jitter, stage, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+}
+
+// the same with a mosaic in front of the colour chain: tiles_dev = [N][4] MosaicTile records (yolo_mosaic_tile_fill),
+// table_dev = the N PrepImage records, of which only the jitter order / factors of each OUTPUT image are read
+int yolo_image_prep_mosaic(const void* src, const void* tiles_dev, const void* table_dev, int N, int S, int fill, int jitter,
+                           void* stage, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1,
+                           float s2, hipStream_t st) {
+    if (N <= 0 || S <= 0 || fill < 0 || fill > 255) return YOLO_ERR_ARG;
+    hipLaunchKernelGGL(k_mosaic, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src,
+                       (const MosaicTile*)tiles_dev, (unsigned char*)stage, S, fill);
+    return color_chain((const PrepImage*)table_dev, N, S, jitter, stage, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
 }
 
 }  // extern "C"

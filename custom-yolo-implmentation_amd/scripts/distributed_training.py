@@ -88,7 +88,10 @@ def main(args):
             val_parquet=os.path.join(data_cfg["processed_dir"], data_cfg["val_parquet"]),
             train_images=data_cfg["train_images"], val_images=data_cfg["val_images"], batch_size=tr_cfg["batch_size"],
             is_test=tr_cfg["is_test"], prefetch_factor=data_cfg.get("prefetch_factor", 2), percent=args.dataset_percent,
-            device=args.device, num_classes=model_cfg["num_classes"])
+            device=args.device, num_classes=model_cfg["num_classes"],
+            # optional key `data.mosaic: {p, gain, fill, min_box, min_visible, max_boxes, close_epochs}`: four-image mosaics
+            # composed from each batch's own images inside the on-device transform (absent = off; the reference has none)
+            mosaic=data_cfg.get("mosaic"))
         # optional key `training.max_grad_norm`: global-norm gradient clipping inside the optimizer step (absent = off).
         # The reference's `training.grad_clip` is dead there (its loop never reads it) and stays ignored here, so a
         # reference config keeps reference numerics.

@@ -22,6 +22,11 @@ class DevicePreppedLoader:
     def __len__(self):
         return len(self.loader)
 
+    def set_epoch(self, epoch, num_epochs):
+        """Per-epoch switches of the transform: the mosaic is off for the last `close_epochs` epochs."""
+        if getattr(self.transform, "mosaic", None) is not None:
+            self.transform.mosaic_on = epoch < num_epochs - self.transform.mosaic["close_epochs"]
+
     def __iter__(self):
         for images, targets in self.loader:
             yield self.transform(images, targets)
@@ -99,7 +104,8 @@ class SyntheticDetectionDataset(Dataset):
 
 
 def get_data_loaders(train_parquet, val_parquet, train_images, val_images, batch_size, is_test=False, prefetch_factor=2,
-                     percent=1.0, device="cpu", num_classes=80, res=640):
+                     percent=1.0, device="cpu", num_classes=80, res=640, mosaic=None):
+    """`mosaic`: the optional `data.mosaic` dict of BatchTransform, for the training transform only."""
     if os.path.exists(train_parquet):
         # the reference's pipeline (src/data/data_loader.py:11-60): workers decode, the transform runs on the device
         from src.data.dataset_loader import DetectionDataset
@@ -114,7 +120,10 @@ def get_data_loaders(train_parquet, val_parquet, train_images, val_images, batch
         kw = dict(num_workers=nw, collate_fn=raw_collate_fn, prefetch_factor=prefetch_factor if nw else None)
         train = DataLoader(train_ds, batch_size=batch_size, shuffle=ts is None, sampler=ts, drop_last=True, **kw)
         val = DataLoader(val_ds, batch_size=batch_size, shuffle=False, sampler=vs, **kw)
-        return DevicePreppedLoader(train, get_train_transforms(res, device)), DevicePreppedLoader(val, get_val_transforms(res, device))
+        return DevicePreppedLoader(train, get_train_transforms(res, device, mosaic=mosaic)), DevicePreppedLoader(val, get_val_transforms(res, device))
+    if mosaic is not None:
+        raise ValueError("data.mosaic needs decoded images: it composes the batch's uint8 images in the on-device transform, and "
+                         f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
     n = 20 if is_test else 256
     train_ds = SyntheticDetectionDataset(max(batch_size, int(n * percent)), res, num_classes, 1234)
     val_ds = SyntheticDetectionDataset(max(batch_size, int(n * percent) // 4), res, num_classes, 4321)

@@ -9,7 +9,9 @@ the workers only decode, and `BatchTransform` uploads the decoded uint8 images o
 antialiased bilinear resize + colour jitter + normalisation as a handful of launches (csrc/image_prep.hip).  The random
 decisions are drawn on the host in torchvision's order (flip: one `torch.rand(1)`; jitter: `torch.randperm(4)` then one
 uniform per factor), boxes follow the geometry (XYWH: x' = W - x - w for a flip, then scaling by 640/W, 640/H) and the
-batch leaves in the format of src/data/collate.py: (images[N,3,S,S], [target dicts with "boxes" (Mi, 5)])."""
+batch leaves in the format of src/data/collate.py: (images[N,3,S,S], [target dicts with "boxes" (Mi, 5)]).
+With `mosaic=` set (opt-in, no reference counterpart), an output is composed of four resized images of its own batch around
+a random centre, in the same launch sequence (`k_mosaic` in the resize launch's place), with its boxes clipped on the host."""
 import math
 
 import numpy as np
@@ -19,10 +21,63 @@ from src.hipops import ops
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
+MOSAIC_DEFAULTS = dict(p=1.0, gain=(0.4, 1.0), fill=114, min_box=2.0, min_visible=0.1, max_boxes=128, close_epochs=0)
 
 
 def _uniform(lo, hi):
     return float(torch.empty(1).uniform_(lo, hi))
+
+
+def mosaic_geometry(draw, i, sizes, flip0, size):
+    """A `sample_mosaic` draw (cx, cy, partners[3], gains[4], flips[3]) for output `i` of a batch whose images have `sizes`
+    [(H, W)] -> the geometry record {"cx", "cy", "tiles": four (source index, flip, tw, th, x0, y0)}.  Tile 0 is image `i`
+    with the flip `sample()` drew for it; tile k is its source resized to (th, tw) = round(gain * size / max(H, W) * (H, W)),
+    at least one pixel, touching the centre with one corner."""
+    cx, cy, partners, gains, flips = draw
+    tiles = []
+    for k, (src, flip) in enumerate(zip((i,) + tuple(partners), (flip0,) + tuple(flips))):
+        h, w = sizes[src]
+        b = size / max(h, w)
+        tw, th = max(1, round(gains[k] * b * w)), max(1, round(gains[k] * b * h))
+        tiles.append((int(src), bool(flip), tw, th, cx if k & 1 else cx - tw, cy if k & 2 else cy - th))
+    return {"cx": int(cx), "cy": int(cy), "tiles": tiles}
+
+
+def mosaic_boxes(record, targets, sizes, size, min_box, min_visible, max_boxes):
+    """Boxes of a mosaic output, (M, 5) float32 (x, y, w, h, label): per tile the source's XYWH boxes flipped, scaled by
+    (tw / W, th / H), moved by (x0, y0) and clipped to what the tile shows (its rectangle within its quadrant and the
+    canvas); a box stays when its clipped sides are >= min_box and >= min_visible of its area is left.  Tile order, source
+    order inside a tile; beyond max_boxes the largest clipped areas stay, in that order."""
+    cx, cy = record["cx"], record["cy"]
+    kept, areas = [], []
+    for k, (src, flip, tw, th, x0, y0) in enumerate(record["tiles"]):
+        h, w = sizes[src]
+        b = targets[src]["boxes"].clone().float().reshape(-1, 4)
+        lo_x, hi_x = max(x0, cx if k & 1 else 0, 0), min(x0 + tw, size if k & 1 else cx, size)
+        lo_y, hi_y = max(y0, cy if k & 2 else 0, 0), min(y0 + th, size if k & 2 else cy, size)
+        if b.shape[0] == 0 or hi_x <= lo_x or hi_y <= lo_y:
+            continue
+        if flip:
+            b[:, 0] = w - (b[:, 0] + b[:, 2])
+        sx, sy = tw / w, th / h
+        b[:, [0, 2]] *= sx
+        b[:, [1, 3]] *= sy
+        full = b[:, 2] * b[:, 3]                            # w * sx * h * sy
+        x1, y1 = b[:, 0] + x0, b[:, 1] + y0
+        x2, y2 = x1 + b[:, 2], y1 + b[:, 3]
+        x1, x2 = x1.clamp(lo_x, hi_x), x2.clamp(lo_x, hi_x)
+        y1, y2 = y1.clamp(lo_y, hi_y), y2.clamp(lo_y, hi_y)
+        cw, ch = x2 - x1, y2 - y1
+        keep = (cw >= min_box) & (ch >= min_box) & (cw * ch / (full + 1e-9) >= min_visible)
+        kept.append(torch.stack([x1, y1, cw, ch, targets[src]["labels"].float().reshape(-1)], 1)[keep])
+        areas.append((cw * ch)[keep])
+    if not kept:
+        return torch.zeros(0, 5)
+    out, area = torch.cat(kept), torch.cat(areas)
+    if out.shape[0] > max_boxes:
+        top = torch.sort(area, descending=True, stable=True).indices[:max_boxes]
+        out = out[torch.sort(top).values]
+    return out
 
 
 class BatchTransform:
@@ -31,10 +86,31 @@ class BatchTransform:
     items before its transform) or None."""
 
     def __init__(self, train, size=640, device="cuda", dtype=torch.float32, flip_p=0.5, brightness=0.2, contrast=0.2,
-                 saturation=0.2, hue=0.1, mean=MEAN, std=STD):
+                 saturation=0.2, hue=0.1, mean=MEAN, std=STD, mosaic=None):
         self.train, self.size, self.device, self.dtype = train, size, torch.device(device), dtype
         self.flip_p, self.jit = flip_p, (brightness, contrast, saturation, hue)
         self.mean, self.std = mean, std
+        # mosaic: None (off: today's path, call for call) or a dict of MOSAIC_DEFAULTS' keys; `mosaic_on` switches it per
+        # epoch (DevicePreppedLoader.set_epoch turns it off for the last `close_epochs` epochs)
+        self.mosaic = None
+        if mosaic is not None:
+            if not train:
+                raise ValueError("mosaic is a training augmentation: the validation transform takes none")
+            unknown = set(mosaic) - set(MOSAIC_DEFAULTS)
+            if unknown:
+                raise ValueError(f"mosaic: unknown keys {sorted(unknown)}; expected {sorted(MOSAIC_DEFAULTS)}")
+            m = {**MOSAIC_DEFAULTS, **mosaic}
+            gain = tuple(float(g) for g in m["gain"])
+            if not 0.0 <= m["p"] <= 1.0:
+                raise ValueError(f"mosaic.p must lie in [0, 1], got {m['p']}")
+            if len(gain) != 2 or not 0.0 < gain[0] <= gain[1] <= 2.0:
+                raise ValueError(f"mosaic.gain must be [lo, hi] with 0 < lo <= hi <= 2, got {m['gain']}")
+            if not 0 <= int(m["fill"]) <= 255 or int(m["max_boxes"]) < 1 or int(m["close_epochs"]) < 0:
+                raise ValueError("mosaic: fill is a uint8 level, max_boxes >= 1 and close_epochs >= 0")
+            self.mosaic = dict(p=float(m["p"]), gain=gain, fill=int(m["fill"]), min_box=float(m["min_box"]),
+                               min_visible=float(m["min_visible"]), max_boxes=int(m["max_boxes"]),
+                               close_epochs=int(m["close_epochs"]))
+        self.mosaic_on = self.mosaic is not None
         self._pinned = None                 # reused pinned upload buffer (one memcpy per image into it, one async H2D per batch)
         self._uploaded = None
 
@@ -48,6 +124,26 @@ class BatchTransform:
         fac = (_uniform(max(0.0, 1 - b), 1 + b), _uniform(max(0.0, 1 - c), 1 + c), _uniform(max(0.0, 1 - s), 1 + s), _uniform(-h, h))
         return flip, order, fac
 
+    def sample_mosaic(self, n):
+        """The mosaic decisions of a batch of `n` images, drawn after its `n` sample() calls (whose sequence is unchanged):
+        per output None (plain) or (cx, cy, partners[3], gains[4], flips[3]) -- one `torch.rand(1) < p`, then three partner
+        indices with replacement, the centre in [S//4, S - S//4], four gains in tile order, the flips of tiles 1-3."""
+        if self.mosaic is None:
+            raise ValueError("sample_mosaic: this transform was built without mosaic=")
+        m, s = self.mosaic, self.size
+        out = []
+        for _ in range(n):
+            if not bool(torch.rand(1) < m["p"]):
+                out.append(None)
+                continue
+            partners = tuple(int(v) for v in torch.randint(0, n, (3,)))
+            cx = int(torch.randint(s // 4, s - s // 4 + 1, (1,)))
+            cy = int(torch.randint(s // 4, s - s // 4 + 1, (1,)))
+            gains = tuple(_uniform(*m["gain"]) for _ in range(4))
+            flips = tuple(bool(torch.rand(1) < self.flip_p) for _ in range(3))
+            out.append((cx, cy, partners, gains, flips))
+        return out
+
     @staticmethod
     def _as_u8(img):
         if isinstance(img, torch.Tensor):
@@ -58,9 +154,16 @@ class BatchTransform:
             raise ValueError("BatchTransform takes decoded RGB images as uint8 (H, W, 3)")
         return t.contiguous()
 
-    def __call__(self, images, targets=None, params=None):
+    def __call__(self, images, targets=None, params=None, mosaic=None):
+        """`params`: the per-image sample() decisions; `mosaic`: per output None (plain), a sample_mosaic() draw or a
+        geometry record (`mosaic_geometry`'s format) -- both are drawn here when not given."""
         imgs = [self._as_u8(i) for i in images]
         params = params if params is not None else [self.sample() for _ in imgs]
+        if mosaic is not None and self.mosaic is None:
+            raise ValueError("mosaic records were passed to a BatchTransform built without mosaic=")
+        use_mosaic = self.mosaic is not None and (self.mosaic_on or mosaic is not None)
+        if use_mosaic and mosaic is None:
+            mosaic = self.sample_mosaic(len(imgs))
         recs, off = [], 0
         for t, (flip, order, fac) in zip(imgs, params):
             h, w = int(t.shape[0]), int(t.shape[1])
@@ -78,11 +181,25 @@ class BatchTransform:
             self._uploaded.record(torch.cuda.current_stream(self.device))
         else:
             flat = torch.cat([t.reshape(-1) for t in imgs])
-        batch = ops.image_prep(flat, recs, self.size, self.train and any(len(p[1]) for p in params), self.dtype, self.mean, self.std)
+        jitter = self.train and any(len(p[1]) for p in params)
+        if use_mosaic:
+            records = self._mosaic_records(mosaic, recs)
+            batch = ops.image_prep_mosaic(flat, recs, self._mosaic_tiles(records, recs), self.size, self.mosaic["fill"], jitter,
+                                          self.dtype, self.mean, self.std)
+        else:
+            records = [None] * len(recs)
+            batch = ops.image_prep(flat, recs, self.size, jitter, self.dtype, self.mean, self.std)
         out_t = None
         if targets is not None:
             out_t = []
-            for tg, (_, h, w, flip, _, _) in zip(targets, recs):
+            sizes = [(r[1], r[2]) for r in recs]
+            for tg, (_, h, w, flip, _, _), rec in zip(targets, recs, records):
+                if rec is not None:
+                    m = self.mosaic
+                    new = {k: v for k, v in tg.items() if k not in ("boxes", "labels")}
+                    new["boxes"] = mosaic_boxes(rec, targets, sizes, self.size, m["min_box"], m["min_visible"], m["max_boxes"])
+                    out_t.append(new)
+                    continue
                 b = tg["boxes"].clone().float().reshape(-1, 4)
                 if flip:
                     b[:, 0] = w - (b[:, 0] + b[:, 2])
@@ -93,9 +210,37 @@ class BatchTransform:
                 out_t.append(new)
         return batch, out_t
 
+    def _mosaic_records(self, mosaic, recs):
+        """Per output None (plain) or its geometry record, from draws or ready records."""
+        if len(mosaic) != len(recs):
+            raise ValueError(f"mosaic: {len(mosaic)} records for {len(recs)} images")
+        sizes = [(r[1], r[2]) for r in recs]
+        out = []
+        for i, m in enumerate(mosaic):
+            if m is not None and not isinstance(m, dict):
+                m = mosaic_geometry(m, i, sizes, recs[i][3], self.size)
+            if m is not None:
+                if len(m["tiles"]) != 4 or any(not 0 <= t[0] < len(recs) or t[2] < 1 or t[3] < 1 for t in m["tiles"]):
+                    raise ValueError(f"mosaic record {i}: four tiles with a source inside the batch and a size of at least 1 x 1")
+            out.append(m)
+        return out
 
-def get_train_transforms(size=640, device="cuda", dtype=torch.float32):
-    return BatchTransform(True, size, device, dtype)
+    def _mosaic_tiles(self, records, recs):
+        """The tile table of ops.image_prep_mosaic; a plain output is the record that reproduces the plain resize: the centre
+        in the bottom-right corner and tile 0 covering the canvas."""
+        s, out = self.size, []
+        for i, m in enumerate(records):
+            if m is None:
+                off, h, w, flip = recs[i][:4]
+                out.append((s, s, [(off, h, w, flip, s, s, 0, 0), None, None, None]))
+            else:
+                out.append((m["cx"], m["cy"], [(recs[src][0], recs[src][1], recs[src][2], flip, tw, th, x0, y0)
+                                               for src, flip, tw, th, x0, y0 in m["tiles"]]))
+        return out
+
+
+def get_train_transforms(size=640, device="cuda", dtype=torch.float32, mosaic=None):
+    return BatchTransform(True, size, device, dtype, mosaic=mosaic)
 
 
 def get_val_transforms(size=640, device="cuda", dtype=torch.float32):

@@ -689,6 +689,14 @@ def scale_inplace(x, scale_dev):
     return x
 
 
+def _prep_table_fill(host, recs):
+    """The PrepImage records of `recs` into the (pinned, zeroed) host table."""
+    for i, (off, h, w, flip, order, fac) in enumerate(recs):
+        o = list(order) + [-1] * (4 - len(order))
+        lib.call("yolo_prep_image_fill", host.data_ptr(), i, int(off), int(h), int(w), int(bool(flip)), *[int(v) for v in o],
+                 *[float(v) for v in fac])
+
+
 def image_prep(src_u8, recs, size, jitter, dtype, mean, std):
     """Batch of decoded uint8 HWC images (flat device buffer `src_u8`; recs = [(offset, H, W, flip, order[4], factors[4])])
     -> normalised (N, 3, size, size) tensor of `dtype`: flip + antialiased bilinear resize + colour jitter + normalise
@@ -696,16 +704,46 @@ def image_prep(src_u8, recs, size, jitter, dtype, mean, std):
     n = len(recs)
     rb = lib.query("yolo_prep_image_bytes")
     host = torch.zeros(n * rb, dtype=torch.uint8).pin_memory()
-    for i, (off, h, w, flip, order, fac) in enumerate(recs):
-        o = list(order) + [-1] * (4 - len(order))
-        lib.call("yolo_prep_image_fill", host.data_ptr(), i, int(off), int(h), int(w), int(bool(flip)), *[int(v) for v in o],
-                 *[float(v) for v in fac])
+    _prep_table_fill(host, recs)
     table = host.to(src_u8.device, non_blocking=True)
     stage = torch.empty((n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
     means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
     out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
     lib.call("yolo_image_prep", _p(src_u8), _p(table), n, size, int(bool(jitter)), _p(stage), _p(means), _p(out), dt(dtype),
              *[float(v) for v in mean], *[float(v) for v in std], _stream(src_u8))
+    return out
+
+
+def image_prep_mosaic(src_u8, recs, tiles, size, fill, jitter, dtype, mean, std):
+    """`image_prep` with a mosaic in front of the colour chain.  recs: as for `image_prep`, one per OUTPUT image (its jitter
+    order and factors are what is read); tiles: per output (cx, cy, [four of (offset, H, W, flip, tw, th, x0, y0) or None]):
+    tile k is that source image resized to (th, tw), placed at (x0, y0) and clipped by quadrant k of the centre (cx, cy); None
+    = no tile, the quadrant is `fill`.  Both tables travel in one pinned buffer and one upload."""
+    st = _stream(src_u8)
+    n = len(recs)
+    if len(tiles) != n:
+        raise ValueError(f"image_prep_mosaic: {n} records but {len(tiles)} tile sets")
+    rb, tb = lib.query("yolo_prep_image_bytes"), lib.query("yolo_mosaic_tile_bytes")
+    host = torch.zeros(n * rb + 4 * n * tb, dtype=torch.uint8).pin_memory()
+    _prep_table_fill(host, recs)
+    for i, (cx, cy, quad) in enumerate(tiles):
+        if len(quad) != 4 or quad[0] is None:
+            raise ValueError("image_prep_mosaic: an output has four tile slots and tile 0 is always present")
+        for k, t in enumerate(quad):
+            if t is None:
+                continue
+            off, h, w, flip, tw, th, x0, y0 = t
+            if off < 0 or off + h * w * 3 > src_u8.numel():
+                raise ValueError(f"image_prep_mosaic: tile {k} of output {i} reads outside the source buffer")
+            lib.call("yolo_mosaic_tile_fill", host.data_ptr() + n * rb, i, k, int(off), int(h), int(w), int(bool(flip)), int(tw),
+                     int(th), int(x0), int(y0), int(cx), int(cy))
+    table = host.to(src_u8.device, non_blocking=True)
+    stage = torch.empty((n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
+    means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
+    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
+    lib.call("yolo_image_prep_mosaic", _p(src_u8), _p(table) + n * rb, _p(table), n, size,
+             int(fill), int(bool(jitter)), _p(stage), _p(means), _p(out), dt(dtype), *[float(v) for v in mean],
+             *[float(v) for v in std], st)
     return out
 
 

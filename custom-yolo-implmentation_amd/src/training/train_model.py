@@ -300,6 +300,8 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
     for epoch in range(initial_epoch, num_epochs):
         if hasattr(train_loader.sampler, "set_epoch"):
             train_loader.sampler.set_epoch(epoch)
+        if hasattr(train_loader, "set_epoch"):      # DevicePreppedLoader: the transform's per-epoch switches (mosaic close-out)
+            train_loader.set_epoch(epoch, num_epochs)
         model.train()
 
         def log_step(i, ld, epoch=epoch):

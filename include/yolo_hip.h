@@ -236,6 +236,14 @@ int yolo_val_match(const float* pred, const int* count, int N, int top_k, const 
 int yolo_prep_image_bytes();
 int yolo_prep_image_fill(void* table_host, int index, long off, int H, int W, int flip, int o0, int o1, int o2, int o3, float brightness, float contrast, float saturation, float hue);
 int yolo_image_prep(const void* src, const void* table_dev, int N, int S, int jitter, void* stage, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
+/* mosaic in front of the same colour chain (no reference counterpart: src/data/transforms.py:4-14 has flip, resize and ColorJitter only):
+   output i is composed of four tiles, each an image of the batch resized to (th, tw) by the filter above and placed at (x0, y0) with one
+   corner on the centre (cx, cy) (tile 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right), clipped by its quadrant, `fill` elsewhere.
+   tiles_dev: [N][4] records (a zeroed record = no tile); table_dev: the N yolo_prep_image_fill records, read for the jitter of output i.
+   The record cx = cy = S, tile 0 = (S, S) at (0, 0) reproduces yolo_image_prep bit for bit */
+int yolo_mosaic_tile_bytes();
+int yolo_mosaic_tile_fill(void* table_host, int image, int tile, long off, int H, int W, int flip, int tw, int th, int x0, int y0, int cx, int cy);
+int yolo_image_prep_mosaic(const void* src, const void* tiles_dev, const void* table_dev, int N, int S, int fill, int jitter, void* stage, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
 
 /* ---- hardware self-tests (instruction semantics the tiled kernels assume; tests/test_gpu_selftest.py; no reference counterpart: model_blocks.py:1) */
 int yolo_selftest_tr16(const void* tile_in, void* out, hipStream_t st);
