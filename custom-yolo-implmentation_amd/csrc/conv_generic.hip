@@ -433,7 +433,7 @@ static dim3 dw_grid(int nrows, int cv) {
 template <bool FLIP>
 static int dw_launch(const void* x, int ldx, const float* w, void* y, int ldy, int N, int H, int W, int C, int dtype,
                      int accumulate, hipStream_t st) {
-    const int fast = dw_strip_launch(FLIP, x, ldx, w, y, ldy, N, H, W, C, dtype, accumulate, nullptr, st);
+    const int fast = dw16_launch(FLIP, x, ldx, w, y, ldy, N, H, W, C, dtype, accumulate, nullptr, st);
     if (fast >= 0) return fast;
     YOLO_DISPATCH_T(dtype, {
         if (vecok<T>(x, ldx, C) && vecok<T>(y, ldy, C)) {
@@ -460,7 +460,7 @@ int yolo_dwconv3x3_fwd(const void* x, int ldx, const float* w, void* y, int ldy,
 // these tensors (fp32, unaligned): nothing was launched, the caller runs yolo_dwconv3x3_fwd + yolo_bn_stats_acc.
 int yolo_dwconv3x3_fwd_stats(const void* x, int ldx, const float* w, void* y, int ldy, float* stats, int N, int H, int W, int C,
                              int dtype, hipStream_t st) {
-    const int fast = dw_strip_launch(false, x, ldx, w, y, ldy, N, H, W, C, dtype, 0, stats, st);
+    const int fast = dw16_launch(false, x, ldx, w, y, ldy, N, H, W, C, dtype, 0, stats, st);
     return fast < 0 ? 1 : fast;
 }
 
@@ -470,7 +470,7 @@ int yolo_dwconv3x3_fwd_stats(const void* x, int ldx, const float* w, void* y, in
 int yolo_dwconv3x3_fwd_act(const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, int N, int H, int W, int C,
                            int act, int dtype, hipStream_t st) {
     if (bias == nullptr || (act != 0 && act != 1)) return YOLO_ERR_ARG;
-    const int fast = dw_strip_launch(false, x, ldx, w, y, ldy, N, H, W, C, dtype, 0, nullptr, st, bias, act);
+    const int fast = dw16_launch(false, x, ldx, w, y, ldy, N, H, W, C, dtype, 0, nullptr, st, bias, act);
     return fast < 0 ? 1 : fast;
 }
 
@@ -493,7 +493,8 @@ int yolo_dwconv3x3_wgrad(const void* x, int ldx, const void* dy, int ldy, float*
     int nrows = N * H;
     int slabs = yolo_dw_wgrad_nslab(N, H);
     int rps = (nrows + slabs - 1) / slabs;
-    const int fast = dw_strip_wgrad_launch(x, ldx, dy, ldy, partial, slabs, N, H, W, C, dtype, st);
+    int nparts = slabs;                                      // partial blocks the kernel writes = what the finalize sums
+    const int fast = dw16_wgrad_launch(x, ldx, dy, ldy, partial, slabs, &nparts, N, H, W, C, dtype, st);
     if (fast > 0) return fast;
     if (fast < 0) YOLO_DISPATCH_T(dtype, {
         if (vecok<T>(x, ldx, C) && vecok<T>(dy, ldy, C)) {
@@ -507,8 +508,37 @@ int yolo_dwconv3x3_wgrad(const void* x, int ldx, const void* dy, int ldy, float*
                                (const T*)dy, ldy, partial, N, H, W, C, rps);
         }
     });
-    hipLaunchKernelGGL(k_dw_wgrad_finalize, dim3(ceil_div(C * 9, 32)), dim3(1024), 0, st, partial, slabs, C * 9, dw);
+    hipLaunchKernelGGL(k_dw_wgrad_finalize, dim3(ceil_div(C * 9, 32)), dim3(1024), 0, st, partial, nparts, C * 9, dw);
     return YOLO_LAUNCH_CHECK();
+}
+
+// process-wide choice of the 16-bit depthwise kernels: 0 = per shape (default), 1 = strip, 2 = rows (also YOLO_DW_KERNEL=strip|rows)
+int yolo_dw_tune_set(int variant) { return dw_tune_set(variant); }
+
+// what the depthwise launches of an (N, H, W, C) map of a 16-bit dtype take.  field 0: the kernel of forward / data gradient,
+// field 12: of the weight gradient (1 rows, 2 strip, 0 the generic kernels: C % 8 != 0); then the rows plan: 1 columns per workgroup, 2 column blocks, 3 channel groups per
+// workgroup, 4 threads per workgroup; forward / data gradient 5 band height, 6 bands per image, 7 grid x; weight gradient
+// 8 band height, 9 bands per image, 10 grid x (= partial blocks); 11 grid y
+int yolo_dw_plan(int N, int H, int W, int C, int field) {
+    if (N < 1 || H < 1 || W < 1 || C < 1) return -1;
+    if (C % 8 || (long)N * H * W * C * 2 >= (1L << 31)) return 0;
+    if (field == 0 || field == 12) return dw_takes_rows(N, H, W, C, field == 12) ? 1 : 2;
+    const DwPlan p = dw_plan(N, H, W, C);
+    const int nslab = yolo_dw_wgrad_nslab(N, H);
+    switch (field) {
+        case 1: return p.ncol;
+        case 2: return p.ncb;
+        case 3: return p.cvb;
+        case 4: return p.wg;
+        case 5: return p.hb;
+        case 6: return p.nb;
+        case 7: return p.grid;
+        case 8: return p.hb_wg;
+        case 9: return p.nb_wg;
+        case 10: return p.grid_wg < nslab ? p.grid_wg : nslab;
+        case 11: return p.ncy;
+        default: return -1;
+    }
 }
 
 }  // extern "C"

@@ -71,11 +71,23 @@ long mfma_wgrad2_ws_elems(int Kpad, int N, int H, int W, int Cin, int OH, int OW
 int mfma_wgrad2_launch(const void* x, int ldx, const void* dy, int ldy, float* part, void* dw_oihw, int dw_dtype, int Kpad,
                        int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, hipStream_t st);
 
-// ---- depthwise strip kernels (dwconv.hip): 16-bit tensors with 8-channel alignment (-1 = does not qualify)
-int dw_strip_launch(bool flip, const void* x, int ldx, const float* w, void* y, int ldy, int N, int H, int W, int C, int dtype,
-                    int accumulate, float* stats, hipStream_t st, const float* bias = nullptr, int act = 0);
-int dw_strip_wgrad_launch(const void* x, int ldx, const void* dy, int ldy, float* partial, int nslab, int N, int H, int W, int C,
-                          int dtype, hipStream_t st);
+// ---- depthwise kernels for 16-bit tensors with 8-channel alignment (dwconv.hip; -1 = does not qualify): the rows or the
+// strip kernels, per shape (dw_takes_rows) unless dw_tune_set / YOLO_DW_KERNEL=strip|rows forces one
+struct DwPlan {                 // rows kernels, one (N, H, W, C) map
+    int cvb, ncy;               // channel groups (of 8) per workgroup, channel blocks (grid y)
+    int ncol, ncb;              // columns per workgroup, column blocks per row
+    int wg;                     // threads per workgroup
+    int hb, nb, grid;           // forward / data gradient: band height, bands per image, grid x
+    int hb_wg, nb_wg, grid_wg;  // weight gradient: the same (grid x = partial blocks written, before the cap by nslab)
+};
+DwPlan dw_plan(int N, int H, int W, int C);
+int dw_tune_set(int variant);    // 0 per shape (default), 1 strip, 2 rows
+bool dw_takes_rows(int N, int H, int W, int C, bool wgrad);
+int dw16_launch(bool flip, const void* x, int ldx, const float* w, void* y, int ldy, int N, int H, int W, int C, int dtype,
+                int accumulate, float* stats, hipStream_t st, const float* bias = nullptr, int act = 0);
+// *nrows = partial blocks written (<= nslab): what k_dw_wgrad_finalize has to sum
+int dw16_wgrad_launch(const void* x, int ldx, const void* dy, int ldy, float* partial, int nslab, int* nrows, int N, int H, int W,
+                      int C, int dtype, hipStream_t st);
 
 // ---- entry points of elementwise.hip that the VALU fallback chains
 extern "C" int yolo_bn_stats_acc(const void* y, int ldy, long npix, int C, int dtype, float* acc, hipStream_t st);

@@ -164,6 +164,16 @@ int yolo_dwconv3x3_fwd_act(const void* x, int ldx, const float* w, const float* 
 int yolo_dwconv3x3_dgrad(const void* dy, int lddy, const float* w, void* dx, int lddx, int N, int H, int W, int C, int accumulate, int dtype, hipStream_t st);
 int yolo_dw_wgrad_nslab(int N, int H);
 int yolo_dwconv3x3_wgrad(const void* x, int ldx, const void* dy, int ldy, float* dw, float* partial, int N, int H, int W, int C, int dtype, hipStream_t st);
+/* ---- depthwise kernel choice and plan (16-bit tensors, C % 8 == 0; the layers are model_blocks.py:183, head.py:56,58; no reference
+   counterpart of the switch itself).  yolo_dw_tune_set: process-wide, 0 = per shape (default: the rows kernels where they were
+   measured ahead, csrc/dwconv.hip dw_takes_rows), 1 = strip kernels, 2 = rows kernels (also the environment variable
+   YOLO_DW_KERNEL=strip|rows, read once); for tuning runs, A/B runs and the parity tests, the training path never calls it.
+   yolo_dw_plan(field): 0 = the kernel forward / data gradient of such a map take, 12 = the weight gradient's (1 rows, 2 strip,
+   0 generic); the rows plan: 1 columns per workgroup, 2 column blocks per row, 3 channel groups (of 8) per workgroup, 4 threads
+   per workgroup; forward / data gradient 5 band height, 6 bands per image, 7 grid x; weight gradient 8 band height, 9 bands per
+   image, 10 grid x (= partial blocks written, <= yolo_dw_wgrad_nslab); 11 grid y */
+int yolo_dw_tune_set(int variant);
+int yolo_dw_plan(int N, int H, int W, int C, int field);
 
 /* ---- BatchNorm2d(eps 1e-3, momentum 0.03) + SiLU/Identity + residual add (model_blocks.py:28-34,62,223-224)
  * pdtype = element type of gamma / beta (and of dgamma / dbeta), bdtype = element type of the running statistics:
