@@ -13,8 +13,9 @@
 //   k_back     : one block per image.  Per matched anchor: DFL cross-entropy pair and its gradient, the quirk IoU (b1_y2 =
 //                h + cy/2, losses.py:20), the soft target at (anchor, class) of the LAST GT mapped there (losses.py:261), and
 //                the IoU gradient that autograd hands to EVERY GT (also those that lost the slot) back through box decode
-//                into the box logits.  The block that finishes LAST (a ticket counter, cleared by k_front) turns the
-//                partials into the three scalars, summing in a fixed order.
+//                into the box logits.  It also writes NaN over the zero box gradient of every anchor whose decoded centre
+//                is NaN (a non-finite box logit), matched or not, as autograd does.  The block that finishes LAST (a ticket
+//                counter, cleared by k_front) turns the partials into the three scalars, summing in a fixed order.
 // fp32 arithmetic, no fma contraction in this file (built with -ffp-contract=off) so the box decode
 // follows the reference's operation order.
 #include "common.h"
@@ -223,6 +224,20 @@ __global__ __launch_bounds__(256) void k_back(LossDims d, const T* __restrict__ 
     const float ccls = d.lambda_cls / (float)d.N / (float)d.A;
     double acc_dfl = 0.0, acc_cls = 0.0;
 
+    // A non-finite box logit must not come back as a finite gradient (fp16 loss scaling looks for it): autograd's softmax
+    // backward gives NaN there even when the anchor is matched by no GT (p (g - sum g p) with p = NaN), while k_front wrote
+    // a zero.  Such an anchor's decoded centre is NaN: cx for the sides l / r, cy for t / b.  The image's centres are
+    // loaded here, all of a thread's in flight at once (A <= PF * 256 in one trip), and looked at after the GT loop, which
+    // hides the round trip.
+    constexpr int PF = 40;
+    const float4* pbn = pbox + (long)n * d.A;
+    float2 pf[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        const int a = threadIdx.x + u * 256;
+        pf[u] = (dn && a < d.A) ? *reinterpret_cast<const float2*>(pbn + a) : make_float2(0.f, 0.f);
+    }
+
     for (int j = wave; j < M; j += 4) {
         const int a = idx[g0 + j];
         bool owner = true;
@@ -303,6 +318,17 @@ __global__ __launch_bounds__(256) void k_back(LossDims d, const T* __restrict__ 
             }
         }
         if (dn) dn[(long)lane * d.A + a] = from_f<T>(gacc * gsc);
+    }
+    if (dn) {   // a matched anchor with a NaN box has NaN in all 64 (its whole IoU chain is NaN): either write may land last
+        auto poison = [&](int a, float cx, float cy) {
+            const bool bx = cx != cx, by = cy != cy;
+            if (!(bx || by)) return;
+            for (int c = 0; c < 4 * REG; ++c)
+                if (((c >> 4) & 1) ? by : bx) dn[(long)c * d.A + a] = from_f<T>(NAN);
+        };
+#pragma unroll
+        for (int u = 0; u < PF; ++u) poison(threadIdx.x + u * 256, pf[u].x, pf[u].y);    // past A: zeros, nothing to do
+        for (int a = threadIdx.x + PF * 256; a < d.A; a += 256) poison(a, pbn[a].x, pbn[a].y);
     }
     if (lane == 0) { w_dfl[wave] = acc_dfl; w_cls[wave] = acc_cls; }
     __syncthreads();

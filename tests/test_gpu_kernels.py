@@ -3,7 +3,9 @@
 The convolution family (dense, stem, depthwise; forward, data and weight gradients, fused inference epilogues) is held to
 the derived per-element bound of tests/strict_compare.py against a float64 reference, attention (every route, its stash
 and its three gradients) to that of tests/strict_attention.py; the BatchNorm leaves are held to tests/strict_bn.py in
-tests/test_gpu_bn.py, and their check() cases here stay as the end-to-end anchor.  The other leaves keep check():
+tests/test_gpu_bn.py, and their check() cases here stay as the end-to-end anchor; the loss kernels are held to
+tests/strict_loss.py in tests/test_gpu_loss.py, the loss tests here stay (the reference's own fp32 goldens, and the 640 x 640
+shape, whose dpreds now also goes through strict_loss with its former limit as the guard).  The other leaves keep check():
 tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
 and round once, the stand-in does the same from the same rounded inputs, so 2 output ulps
 (bf16: 2^-7, f16: 2^-10 relative) of the tensor's max magnitude.  Integer outputs (pool argmax,
@@ -16,6 +18,7 @@ import torch
 import emulated_ops as emu
 import strict_attention as sa
 import strict_compare as sc
+import strict_loss as sl
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -697,7 +700,7 @@ def _pack(gts):
     return PackedTargets([g.to(DEV) for g in gts], DEV)
 
 
-def _loss_case(preds, gts, anchors, strides, nc, dtype, lam=(1.5, 1.0)):
+def _loss_case(preds, gts, anchors, strides, nc, dtype, lam=(1.5, 1.0), strict=None):
     o = ops()
     pk = _pack(gts)
     p = preds.to(dtype)
@@ -707,6 +710,12 @@ def _loss_case(preds, gts, anchors, strides, nc, dtype, lam=(1.5, 1.0)):
                                           lam[0], lam[1], True)
     n, _, a = preds.shape
     idx = ws[n * a * 16:n * a * 16 + 4 * max(pk.n_gt, 1)].view(torch.int32)[:pk.n_gt].cpu()
+    if strict:                                               # every stage within the derived limits of strict_loss.py
+        case = sl.Case(preds, anchors, strides, gts, nc, dtype, f"{strict} {str(dtype)[6:]}", lam)
+        assert sl.guard_ok(case)
+        pbox = ws[:n * a * 16].view(torch.float32).view(n, a, 4).cpu()
+        ref = sl.evaluate(case, idx.long(), pbox)
+        sl.verify(case, out.cpu(), dp.cpu(), pbox, idx, old=sl.old_abs(ref["dp"], dtype))
     return out.cpu(), dp.float().cpu(), ref_out, ref_dp.float(), idx
 
 
@@ -742,7 +751,7 @@ def test_loss_random_s640_shape(dtype):
         m = int(torch.randint(1, 21, (1,), generator=g))
         gts.append(torch.cat([torch.rand(m, 2, generator=g) * 640, torch.rand(m, 2, generator=g) * 256 + 8,
                               torch.randint(0, 80, (m, 1), generator=g).float()], 1))
-    out, dp, ref_out, ref_dp, idx = _loss_case(preds, gts, a.t().contiguous(), s.t().contiguous(), 80, dtype)
+    out, dp, ref_out, ref_dp, idx = _loss_case(preds, gts, a.t().contiguous(), s.t().contiguous(), 80, dtype, strict="s640 seed 70")
     assert torch.allclose(out, ref_out, rtol=1e-4 if dtype == torch.float32 else 1e-3, atol=1e-6), (out, ref_out)
     lim = 1e-4 if dtype == torch.float32 else 2.0 ** -6
     err = float((dp - ref_dp).abs().max()) / float(ref_dp.abs().max())
@@ -760,6 +769,12 @@ def test_module_level_loss_helpers_match_the_oracle_with_gradients():
     b2 = b1 + torch.randn(m, 4, generator=g) * 6
     b2[:, 2:] = b2[:, 2:].abs() + 1
     b2[:7] = b1[:7] + 500                                   # disjoint boxes: clamp branch
+    # rows the random ones never contain (dyadic values: every corner is exact in fp32): both x corners tie and both y
+    # corners tie (min / max split their gradient evenly), and boxes that touch in x (the >= 0 side of the clamp)
+    b1[7], b2[7] = torch.tensor([64.0, 8.0, 32.0, 16.0]), torch.tensor([64.0, 10.0, 32.0, 20.0])     # y2 slip: 16 + 4 = 10 + 10
+    b1[8], b2[8] = torch.tensor([40.0, 24.0, 16.0, 32.0]), torch.tensor([40.0, 20.0, 16.0, 24.0])
+    b1[9], b2[9] = torch.tensor([32.0, 8.0, 16.0, 16.0]), torch.tensor([44.0, 8.0, 8.0, 8.0])         # x2 = 40 = their x1
+    b1[10], b2[10] = torch.tensor([96.0, 16.0, 8.0, 24.0]), torch.tensor([88.0, 16.0, 8.0, 8.0])      # x1 = 92 = their x2
     w = torch.randn(m, generator=g)
 
     def both(fn_dev, fn_ref, args, weight=None):
@@ -781,6 +796,7 @@ def test_module_level_loss_helpers_match_the_oracle_with_gradients():
     both(lambda p, t: quality_focal_loss(p, t, beta=1.5), lambda p, t: ol.qfl_sum(p, t, 1.5), (logits, target))
     dist_logits = torch.randn(91, 16, generator=g)
     tv = torch.rand(91, generator=g) * 14.98
+    tv[:6] = torch.tensor([0.0, 3.0, 14.0, 14.98, 1.0, 0.0])  # the edges: 0, exact integers (right weight 0), 14.98
     both(distribution_focal_loss, ol.dfl_side, (dist_logits, tv))
 
 
