@@ -5,7 +5,9 @@ the derived per-element bound of tests/strict_compare.py against a float64 refer
 and its three gradients) to that of tests/strict_attention.py; the BatchNorm leaves are held to tests/strict_bn.py in
 tests/test_gpu_bn.py, and their check() cases here stay as the end-to-end anchor; the loss kernels are held to
 tests/strict_loss.py in tests/test_gpu_loss.py, the loss tests here stay (the reference's own fp32 goldens, and the 640 x 640
-shape, whose dpreds now also goes through strict_loss with its former limit as the guard).  The other leaves keep check():
+shape, whose dpreds now also goes through strict_loss with its former limit as the guard); the pool, upsample, copy, add_n,
+transpose, bucket and weight-pack leaves are held to tests/strict_move.py in tests/test_gpu_move.py (the pool's argmax compared
+exactly, slices with their neighbours), their cases here stay as the anchor.  check():
 tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
 and round once, the stand-in does the same from the same rounded inputs, so 2 output ulps
 (bf16: 2^-7, f16: 2^-10 relative) of the tensor's max magnitude.  Integer outputs (pool argmax,
@@ -19,6 +21,7 @@ import emulated_ops as emu
 import strict_attention as sa
 import strict_compare as sc
 import strict_loss as sl
+import strict_move as sm
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -451,6 +454,7 @@ def test_maxpool5_and_upsample(dtype):
     out, idx = o.maxpool5_fwd(dev(x))
     out_ref, idx_ref = emu.maxpool5_fwd(x)
     assert torch.equal(out.cpu(), out_ref)
+    assert torch.equal(sm.aten_index(idx.permute(0, 3, 1, 2).cpu()), idx_ref)      # the argmax itself, not only what it routes
     dout = nhwc(rnd(2, 24, 9, 10, seed=41).to(dtype))
     check(o.maxpool5_bwd(dev(dout), idx), emu.maxpool5_bwd(dout, idx_ref), dtype, "maxpool5_bwd (tie routing)", mult=2.0)
     up = o.upsample2x_fwd(dev(x))
