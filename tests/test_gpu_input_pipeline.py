@@ -7,7 +7,8 @@ distance of a level boundary may come out one level apart (and the hue round tri
 outputs must agree exactly on >= 99.5 % of the elements after the resize alone and >= 97 % after the four colour ops
 (resampling with dyadic weights produces exact .5 ties whose rounding depends on the summation order, and every
 further quantisation step can move such a pixel once more; the hue round trip scales a one-level difference of one
-channel by up to the saturation gain), within 3 levels (3 / 255 / 0.224 = 0.053) after the resize and 6 after the chain."""
+channel by up to the saturation gain), within 3 levels (3 / 255 / 0.224 = 0.053) after the resize and 6 after the chain.  This is the end-to-end anchor; every stage on
+its own is held to its per-pixel set of allowed levels in tests/test_gpu_image.py (tests/strict_image.py)."""
 import time
 
 import numpy as np

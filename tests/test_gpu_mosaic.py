@@ -8,7 +8,8 @@ reference, so >= 99.5 % of ALL elements of the batch agree exactly and none is m
 a record that describes a plain resize -- every bit of the plain transform's output.
 
 Measured on an MI355X with these inputs (each test prints its figures): G2 99.994 % exact and at most 1 level after the resize
-alone, 99.73 % and 3 levels after the four colour ops; G3 (S = 64, sampled records) 99.997 % and 1 level."""
+alone, 99.73 % and 3 levels after the four colour ops; G3 (S = 64, sampled records) 99.997 % and 1 level.  Stage by stage, with
+nothing propagating, the mosaic's tile pixels are held to the resize's sets of allowed levels in tests/test_gpu_image.py."""
 import os
 
 import numpy as np
