@@ -19,10 +19,11 @@
 // fp32 arithmetic, no fma contraction in this file (built with -ffp-contract=off) so the box decode
 // follows the reference's operation order.
 #include "common.h"
+#include "loss_shared.h"
 
 namespace {
 
-constexpr int REG = 16;
+constexpr int REG = LOSS_REG;
 constexpr float QEPS = 1e-12f;
 
 struct LossDims {
@@ -38,23 +39,7 @@ __device__ __forceinline__ void decode_block(const LossDims& d, int block, const
     int a = (int)(i % d.A);
     long n = i / d.A;
     const T* p = preds + n * (long)(4 * REG + d.nc) * d.A + a;
-    float e[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        float x[REG], mx = -INFINITY;
-#pragma unroll
-        for (int b = 0; b < REG; ++b) { x[b] = to_f<T>(p[(long)(s * REG + b) * d.A]); mx = fmaxf(mx, x[b]); }
-        float sum = 0.f;
-#pragma unroll
-        for (int b = 0; b < REG; ++b) { x[b] = expf(x[b] - mx); sum += x[b]; }
-        float ex = 0.f;
-#pragma unroll
-        for (int b = 0; b < REG; ++b) ex += (x[b] / sum) * (float)b;
-        e[s] = ex;
-    }
-    float ax = to_f<T>(anchors[a]), ay = to_f<T>(anchors[d.A + a]), st = to_f<T>(strides[a]);
-    float x1 = (ax - e[0]) * st, y1 = (ay - e[1]) * st, x2 = (ax + e[2]) * st, y2 = (ay + e[3]) * st;
-    pbox[i] = make_float4((x1 + x2) / 2.f, (y1 + y2) / 2.f, x2 - x1, y2 - y1);
+    pbox[i] = decode_anchor<T>(p, d.A, to_f<T>(anchors[a]), to_f<T>(anchors[d.A + a]), to_f<T>(strides[a]));
 }
 
 // assignment of GT row j (of image n) by ONE wave: argmin over the image's anchors, lowest index among equal distances,
@@ -245,16 +230,8 @@ __global__ __launch_bounds__(256) void k_back(LossDims d, const T* __restrict__ 
         if (!owner) continue;                                   // wave-uniform
         // softmax of this lane's side over its 16 bins
         float x = to_f<T>(pn[(long)lane * d.A + a]);
-        float mx = x;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        float ex = expf(x - mx), sum = ex;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-        float p = ex / sum, lse = mx + logf(sum);
-        float ev = p * (float)bin;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ev += __shfl_xor(ev, o, 64);           // expectation of my side
+        float p, lse, ev;                                       // my side's softmax, log-sum-exp and expectation
+        side_softmax(x, bin, p, lse, ev);
         const float ax = to_f<T>(anchors[a]), ay = to_f<T>(anchors[d.A + a]), st = to_f<T>(strides[a]);
         const float4 pb = pbox[(long)n * d.A + a];
         float gacc = 0.f;                                        // d total / d logit(lane)
@@ -270,17 +247,11 @@ __global__ __launch_bounds__(256) void k_back(LossDims d, const T* __restrict__ 
             // ---- DFL (losses.py:226-253)
             float tl = ax - gx1 / st, tt = ay - gy1 / st, tr = gx2 / st - ax, tb = gy2 / st - ay;
             float tv = side == 0 ? tl : side == 1 ? tt : side == 2 ? tr : tb;
-            tv = fminf(fmaxf(tv, 0.f), (float)(REG - 1) - 0.01f);
-            int lo = (int)tv;
-            float wl = (float)(lo + 1) - tv, wr = tv - (float)lo;
-            float contrib = (bin == lo ? wl * (lse - x) : 0.f) + (bin == lo + 1 ? wr * (lse - x) : 0.f);
-            float side_loss = contrib;
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) side_loss += __shfl_xor(side_loss, o, 64);
-            float all_sides = side_loss + __shfl_xor(side_loss, 16, 64);
-            all_sides += __shfl_xor(all_sides, 32, 64);
+            float contrib, gbody;
+            dfl_pair(tv, bin, lse - x, p, contrib, gbody);
+            const float all_sides = sides_sum(contrib);
             if (lane == 0) acc_dfl += (double)all_sides * 0.25 / (double)M;
-            gacc += cdfl * (p - (bin == lo ? wl : 0.f) - (bin == lo + 1 ? wr : 0.f));
+            gacc += cdfl * gbody;
             // ---- quirk IoU of (pred box, GT) and its gradient (losses.py:17-40)
             const float X1 = pb.x - pb.z / 2.f, Y1 = pb.y - pb.w / 2.f, X2 = pb.x + pb.z / 2.f, Y2 = pb.w + pb.y / 2.f;
             const float iwr = fminf(X2, gx2) - fmaxf(X1, gx1), ihr = fminf(Y2, gy2) - fmaxf(Y1, gy1);

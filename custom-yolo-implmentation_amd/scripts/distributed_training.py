@@ -18,7 +18,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import torch  # noqa: E402
 
 from src.data.data_loader import get_data_loaders  # noqa: E402
-from src.model.losses import YoloDFLQFLoss  # noqa: E402
+from src.model.losses import YoloDFLQFLoss, YoloTALoss  # noqa: E402
 from src.model.model_builder import Model  # noqa: E402
 from src.training.distributed_setup import cleanup_distribute_mode, init_distributed_mode  # noqa: E402
 from src.training.train_model import train  # noqa: E402
@@ -36,6 +36,36 @@ def optimizer_choice(tr_cfg):
     reference config's value and the default, or "sgd") and the optional `training.sgd: {momentum, nesterov, warmup_steps,
     warmup_momentum, warmup_lr_scale}`.  The reference carries the first key but never reads it."""
     return dict(optimizer=tr_cfg.get("optimizer", "adamw"), sgd=tr_cfg.get("sgd", None))
+
+
+_LOSS_KEYS = ("assigner", "topk", "alpha", "beta", "box", "cls", "dfl")
+
+
+def build_criterion(tr_cfg, num_classes):
+    """The criterion of the training section.  Optional key `training.loss: {assigner: "tal", topk, alpha, beta, box, cls,
+    dfl}` selects YoloTALoss (task-aligned top-k assignment, CIoU box term, normalised soft class targets; box / cls / dfl
+    are its three weights).  Absent, or `assigner: "nearest"` alone: the reference's YoloDFLQFLoss with `training.weights`,
+    as before.  Unknown keys and values raise."""
+    loss_cfg = tr_cfg.get("loss", None)
+    if loss_cfg is not None:
+        if not isinstance(loss_cfg, dict):
+            raise ValueError(f"training.loss must be a mapping with some of {list(_LOSS_KEYS)}")
+        unknown = sorted(set(loss_cfg) - set(_LOSS_KEYS))
+        if unknown:
+            raise ValueError(f"training.loss: unknown keys {unknown}; expected some of {list(_LOSS_KEYS)}")
+        assigner = loss_cfg.get("assigner", "tal")
+        if assigner not in ("tal", "nearest"):
+            raise ValueError(f"training.loss.assigner: {assigner!r}; expected \"tal\" or \"nearest\"")
+        if assigner == "nearest":
+            extra = sorted(set(loss_cfg) - {"assigner"})
+            if extra:
+                raise ValueError(f"training.loss: {extra} belong to assigner \"tal\"; the nearest-centre loss reads training.weights")
+        else:
+            return YoloTALoss(num_classes=num_classes, lambda_box=loss_cfg.get("box", 7.5), lambda_cls=loss_cfg.get("cls", 0.5),
+                              lambda_dfl=loss_cfg.get("dfl", 1.5), topk=loss_cfg.get("topk", 10), alpha=loss_cfg.get("alpha", 0.5),
+                              beta=loss_cfg.get("beta", 6.0))
+    return YoloDFLQFLoss(num_classes=num_classes, lambda_box=tr_cfg["weights"].get("bbox_loss", 1.5),
+                         lambda_cls=tr_cfg["weights"].get("cls_loss", 1.0))
 
 
 def main(args):
@@ -114,8 +144,7 @@ def main(args):
             path = find_latest_checkpoint(ckpt_dir)
             initial_epoch = load_checkpoint(model, optimizer, path, map_location=args.device, ema=ema)
             print(f"[INFO] Loaded model and optimizer from checkpoint at epoch {initial_epoch} from {path}")
-        criterion = YoloDFLQFLoss(num_classes=model_cfg["num_classes"], lambda_box=tr_cfg["weights"].get("bbox_loss", 1.5),
-                                  lambda_cls=tr_cfg["weights"].get("cls_loss", 1.0))
+        criterion = build_criterion(tr_cfg, model_cfg["num_classes"])
         train(model=model, train_loader=train_loader, val_loader=val_loader, optimizer=optimizer, scheduler=scheduler,
               criterion=criterion, initial_epoch=initial_epoch, num_epochs=initial_epoch + tr_cfg["epochs"], device=gpu,
               num_classes=model_cfg["num_classes"], rank=rank, use_wandb=use_wandb, wandb_instance=run,

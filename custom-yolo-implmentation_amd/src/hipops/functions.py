@@ -848,3 +848,28 @@ class DflQflLoss(torch.autograd.Function):
         if not UNIT_LOSS_SEED:      # a seed of exactly 1.0 (see UNIT_LOSS_SEED) leaves every 16-bit value as it is: no pass over dpreds
             ops.scale_inplace(dpreds, g_total.reshape(1).float())
         return dpreds, None, None, None, None, None, None
+
+
+class TalLoss(torch.autograd.Function):
+    """YoloTALoss value and gradient from one fused pass (csrc/loss_tal.hip).
+    Returns (total, scalars[4]); scalars = (total, box, cls, dfl) detached.  LOSS_SCALE and UNIT_LOSS_SEED as in DflQflLoss."""
+
+    @staticmethod
+    def forward(ctx, preds, anchors, strides, packed, nc, hyper):
+        gt, gt_off, gt_img, n_gt = packed
+        want = ctx.needs_input_grad[0]
+        out, dpreds, _ = ops.loss_tal_fwd_bwd(preds.contiguous(), anchors, strides, gt, gt_off, gt_img, n_gt, nc, *hyper,
+                                              want, LOSS_SCALE if want else None)
+        ctx.dpreds = dpreds
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_scalars):
+        dpreds = ctx.dpreds
+        ctx.dpreds = None
+        if dpreds is None:
+            return (None,) * 6
+        if not UNIT_LOSS_SEED:
+            ops.scale_inplace(dpreds, g_total.reshape(1).float())
+        return dpreds, None, None, None, None, None

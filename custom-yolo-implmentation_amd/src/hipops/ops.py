@@ -639,6 +639,44 @@ def loss_fwd_bwd(preds, anchors, strides, gt, gt_off, gt_img, n_gt, nc, lambda_d
     return out, dpreds, ws
 
 
+TAL_KMAX = 16      # list entries per GT row in the workspace of yolo_loss_tal (csrc/loss_tal.hip KMAX)
+
+
+def loss_tal_fwd_bwd(preds, anchors, strides, gt, gt_off, gt_img, n_gt, nc, topk, alpha, beta, lambda_box, lambda_cls,
+                     lambda_dfl, want_grad, grad_scale=None):
+    """-> (out[4] fp32 = total, box (CIoU), cls, dfl ; dpreds or None ; workspace).  Task-aligned assignment; `grad_scale`
+    as in loss_fwd_bwd."""
+    assert grad_scale is None or (grad_scale.dtype == torch.float32 and grad_scale.is_cuda)
+    n, cp, a = preds.shape
+    assert preds.is_contiguous() and cp == 64 + nc
+    anchors = anchors.to(preds.dtype).contiguous()
+    strides = strides.to(preds.dtype).contiguous()
+    ws = torch.empty(lib.query("yolo_loss_tal_workspace_bytes", n, a, n_gt), dtype=torch.uint8, device=preds.device)
+    out = _f32(4, preds.device)
+    dpreds = torch.empty_like(preds) if want_grad else None
+    lib.call("yolo_loss_tal", _p(preds), _p(anchors), _p(strides), dt(preds), n, nc, a, _p(gt), _p(gt_off), _p(gt_img), n_gt,
+             int(topk), float(alpha), float(beta), float(lambda_box), float(lambda_cls), float(lambda_dfl), _p(dpreds), _p(out),
+             _p(ws), _p(grad_scale), _stream(preds))
+    return out, dpreds, ws
+
+
+def loss_tal_workspace_views(ws, n, a, n_gt):
+    """the buffers yolo_loss_tal leaves in its workspace, in the order csrc/loss_tal.hip carves them (every one rounded up to
+    16 bytes) -> dict of views: pbox (N, A, 4) f32, owner (N, A) i64, tl (N, A, 2) i32 = (label | -1 none | -2 poisoned, t
+    bits), la / lal / lio / ebox / edfl (G, 16), cnt / gma / gmi / gts (G,), partial (2048,) f64, tss (1,) f32"""
+    na, g, k = n * a, max(n_gt, 1), TAL_KMAX
+    spec = [("pbox", na * 16, torch.float32, (n, a, 4)), ("owner", na * 8, torch.int64, (n, a)), ("tl", na * 8, torch.int32, (n, a, 2)),
+            ("la", g * k * 4, torch.int32, (g, k)), ("lal", g * k * 4, torch.float32, (g, k)), ("lio", g * k * 4, torch.float32, (g, k)),
+            ("ebox", g * k * 4, torch.float32, (g, k)), ("edfl", g * k * 4, torch.float32, (g, k)),
+            ("cnt", g * 4, torch.int32, (g,)), ("gma", g * 4, torch.float32, (g,)), ("gmi", g * 4, torch.float32, (g,)),
+            ("gts", g * 4, torch.float32, (g,)), ("partial", 2048 * 8, torch.float64, (2048,)), ("tss", 4, torch.float32, (1,))]
+    views, off = {}, 0
+    for name, nbytes, dtype, shape in spec:
+        views[name] = ws[off:off + nbytes].view(dtype).view(shape)
+        off += (nbytes + 15) // 16 * 16
+    return views
+
+
 def _f32c(t):
     if t.dtype != torch.float32 or not t.is_contiguous():
         raise RuntimeError("the stand-alone loss helpers take contiguous fp32 tensors")

@@ -115,13 +115,18 @@ class StaticTargets:
 
 class LazyLossDict(dict):
     """{"total_loss","box_loss","cls_loss": float}.  The three scalars stay on the device until first
-    read and then arrive with ONE device->host copy (the reference does three .item() syncs, :278-280)."""
+    read and then arrive with ONE device->host copy (the reference does three .item() syncs, :278-280).
+    With the four scalars of YoloTALoss the dict also carries "dfl_loss"."""
 
     _KEYS = ("total_loss", "box_loss", "cls_loss")
 
-    def __init__(self, scalars):
+    def __init__(self, scalars, keys=None):
         super().__init__()
         self._scalars = scalars
+        if keys is None and scalars is not None and scalars.numel() == 4:      # YoloTALoss's scalars, wherever they come from
+            keys = self._KEYS + ("dfl_loss",)
+        if keys is not None:
+            self._KEYS = tuple(keys)
 
     def _fill(self):
         if self._scalars is not None:
@@ -143,7 +148,7 @@ class LazyLossDict(dict):
         return dict.__iter__(self)
 
     def __len__(self):
-        return 3
+        return len(self._KEYS)
 
     def __contains__(self, k):
         return k in self._KEYS
@@ -186,3 +191,35 @@ class YoloDFLQFLoss(nn.Module):
         total, scalars = F_.DflQflLoss.apply(preds, anchors, strides, packed.as_tuple(), self.num_classes,
                                              float(self.lambda_dfl), float(self.lambda_cls))
         return total, LazyLossDict(scalars)
+
+
+class YoloTALoss(nn.Module):
+    """Task-aligned assignment (the `topk` anchors inside each GT with the largest sigmoid(cls)^alpha * IoU^beta; a contested
+    anchor goes to the GT with the larger IoU), a CIoU box term, BCE class targets t = align * max_iou / max_align, and DFL
+    weighted by t; every term divided by max(sum t, 1).  Same call as YoloDFLQFLoss; the dict carries "box_loss" (the CIoU
+    term), "cls_loss" and "dfl_loss".  One fused HIP pass (yolo_loss_tal), capturable."""
+
+    MAX_TOPK = 16
+
+    def __init__(self, num_classes=171, lambda_box=7.5, lambda_cls=0.5, lambda_dfl=1.5, topk=10, alpha=0.5, beta=6.0, reg_max=16):
+        super().__init__()
+        if reg_max != 16:
+            raise ValueError("the loss kernel is built for reg_max = 16 (the head's DFL width)")
+        if int(topk) != topk or not 1 <= int(topk) <= self.MAX_TOPK:
+            raise ValueError(f"topk must be an integer in 1..{self.MAX_TOPK} (the kernel keeps {self.MAX_TOPK} list entries per box)")
+        if not (alpha >= 0 and beta >= 0):
+            raise ValueError("alpha and beta must be >= 0")
+        self.num_classes = num_classes
+        self.lambda_box, self.lambda_cls, self.lambda_dfl = lambda_box, lambda_cls, lambda_dfl
+        self.topk, self.alpha, self.beta = int(topk), alpha, beta
+        self.reg_max = reg_max
+
+    def forward(self, preds, gt_boxes_list, anchors, strides):
+        packed = gt_boxes_list if isinstance(gt_boxes_list, (PackedTargets, StaticTargets)) \
+            else PackedTargets(gt_boxes_list, preds.device)
+        if packed.n_img != preds.shape[0]:
+            raise ValueError("one GT tensor per image is required")
+        hyper = (self.topk, float(self.alpha), float(self.beta), float(self.lambda_box), float(self.lambda_cls),
+                 float(self.lambda_dfl))
+        total, scalars = F_.TalLoss.apply(preds, anchors, strides, packed.as_tuple(), self.num_classes, hyper)
+        return total, LazyLossDict(scalars, ("total_loss", "box_loss", "cls_loss", "dfl_loss"))

@@ -217,6 +217,12 @@ int yolo_attn_bwd(const void* qkv, int ldq, const void* o, int ldo, const void* 
 size_t yolo_loss_workspace_bytes(int N, int A, int G);
 int yolo_loss_dfl_qfl(const void* preds, const void* anchors, const void* strides, int dtype, int N, int nc, int A, const float* gt, const int* gt_off, const int* gt_img, int G, float lambda_dfl, float lambda_cls, void* dpreds, float* out, void* workspace, const float* grad_scale, hipStream_t st);
 
+/* ---- YoloTALoss forward+gradient: a second criterion behind the call of the reference's one (losses.py:93-281, called at
+   train_model.py:245): task-aligned top-k assignment, CIoU box term, normalised soft class targets.
+   Same buffers as yolo_loss_dfl_qfl; out: fp32[4] = {total, box (CIoU), cls (BCE), dfl}; 1 <= topk <= 16 */
+size_t yolo_loss_tal_workspace_bytes(int N, int A, int G);
+int yolo_loss_tal(const void* preds, const void* anchors, const void* strides, int dtype, int N, int nc, int A, const float* gt, const int* gt_off, const int* gt_img, int G, int topk, float alpha, float beta, float lambda_box, float lambda_cls, float lambda_dfl, void* dpreds, float* out, void* workspace, const float* grad_scale, hipStream_t st);
+
 /* the reference's module-level loss helpers as stand-alone differentiable fp32 ops (notebook API; the training step uses
    the fused pass above): bbox_iou (losses.py:9-40, incl. the b1_y2 slip), quality_focal_loss (:46-57),
    distribution_focal_loss (:63-78).  g == null: forward; g = device gradient (per row for bbox_iou, one scalar for the
