@@ -81,6 +81,26 @@ static inline int yolo_allow_dyn_lds(const void* fn, size_t bytes, unsigned long
     return YOLO_OK;
 }
 
+// One launch of a kernel that needs the attribute: allow, launch, check.  The kernel is a template ARGUMENT so that every
+// kernel instantiation gets its own `done` mask (a function parameter would share one among kernels of the same signature).
+template <auto KERNEL, typename... Args>
+static inline int launch_dyn_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, Args... args) {
+    static unsigned long long done = 0;
+    if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(KERNEL), lds_bytes, done)) return e;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds_bytes, st, args...);
+    return YOLO_LAUNCH_CHECK();
+}
+
+// Raw buffer descriptor over `bytes` bytes at base.  BUF_FLAGS, word 3: DATA_FORMAT = 32-bit (bit 17), all else 0 -- no stride,
+// swizzle or thread-id addressing: an access is in range while its unsigned byte offset (vector + scalar) is below `bytes`, a
+// lane out of range reads zero without a fetch.  The host guards keep `bytes` below 2^31, so BUF_OOB is out of range everywhere.
+constexpr int BUF_FLAGS = 0x00020000;
+constexpr int BUF_OOB = (int)0x80000000;
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_desc(const T* base, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, bytes, BUF_FLAGS);
+}
+
 // Zero fill as a KERNEL.  hipMemsetAsync becomes a memset node when the stream is captured into a hipGraph, and on
 // this stack replays of such a graph did not always order that node before the kernels that accumulate into the
 // buffer (BatchNorm statistics came out wrong from the second replay on, run-dependent).  Kernel nodes of a

@@ -1,11 +1,11 @@
 // Device-side pieces shared by the MFMA conv kernels (conv_mfma / conv_ring / conv_rows / conv_halo / conv_up2.hip and the
-// fused stem of stem.hip): MFMA wrappers, the packed geometry passed by value, the XCD-aware tile order, and the ONE copy of
-// the kernels' tail -- bias gather, linear pixel walk, pixel store (ConvEpi, store_pixel_blocks) and the BatchNorm
-// statistics epilogue (conv_stats_epilogue) -- plus the accumulate dispatch of their launchers (with_acc).
+// fused stem of stem.hip): MFMA wrappers, the packed geometry passed by value, and the ONE copy of the kernels' tail -- bias
+// gather, linear pixel walk, pixel store (ConvEpi, store_pixel_blocks) and the BatchNorm statistics epilogue
+// (conv_stats_epilogue) -- plus the accumulate dispatch (with_acc).  Ring idiom and tile decode: conv_stage.h.
 #pragma once
 #include <cstdlib>
-#include <type_traits>
 #include "conv_host.h"
+#include "conv_stage.h"
 
 namespace {
 
@@ -29,9 +29,9 @@ template <> struct mfma_ops<f16_t> {
 
 constexpr int BM = 128;    // destination pixels per workgroup
 constexpr int BK = 32;     // K elements per step (one MFMA K)
-constexpr int LDSROW = 32; // elements per LDS row: unpadded 64-byte rows whose four 16-byte chunks are XOR-swizzled
-                           // by (-(row >> 2)) & 3 -- conflict-free for ds_read_b128 fragment reads (16 rows x 1 chunk
-                           // per lane group) and for the ds_write_b128 staging (2 rows x 4 chunks per 8 lanes)
+constexpr int LDSROW = 32; // elements per LDS row: THE 64-byte-row image, unpadded rows whose four 16-byte chunks are XOR-swizzled
+                           // by (-(row >> 2)) & 3 -- conflict-free for ds_read_b128 fragment reads (16 rows x 1 chunk per lane
+                           // group) and for ds_write_b128 staging (2 rows x 4 chunks per 8 lanes); 16 rows = one LDS-DMA piece
 
 // What the kernels' shared tail reads, declared once and embedded in every family's kernarg struct (to_epi fills it)
 struct ConvEpi {
@@ -54,17 +54,11 @@ struct GeomDev {           // ConvGeom with the tap offsets packed (no dynamic i
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// bijective XCD-aware remap (guide T1): blocks that share an XCD get a contiguous range of tiles
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-// LDS-DMA: 16 bytes per lane from a buffer descriptor straight into LDS at lds_base + 16*lane (wave-uniform base).
-// Wrapped so that the host compilation pass never sees the device-only builtin.
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, void* lds_base, int voffset, int soffset) {
+// LDS-DMA as the BUILTIN, which hipcc sees and waits for by itself (the ring kernels use lds_dma_piece, conv_stage.h): 16 bytes
+// per lane from a descriptor into LDS at dst + 16*lane (wave-uniform dst).  Wrapped: the host pass must not see the builtin.
+__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, void* dst, int voffset, int soffset) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, voffset, soffset, 0, 0);
 #endif
 }
 

@@ -5,8 +5,8 @@
 // (TH+2) x 18 halo patch in LDS (96-byte pixel rows: 64 B payload + 32 B pad, which makes every ds_read_b128
 // fragment read conflict-free at ANY pixel offset), and the taps are nine scalar offsets into that patch -- no
 // address arithmetic, no second global read.  Weights stream through a double-buffered [BN][32] tile per (chunk, tap)
-// exactly as in k_conv_mfma (64-byte rows, XOR chunk swizzle).  Forward and stride-1 data gradient share it
-// (ConvGeom tap list + packed weights).  Wave tile 64 pixels (4 output rows) x 64 channels; waves = TH/4 x BN/64.
+// in the 64-byte-row image of k_conv_mfma (LDSROW in conv_dev.h).  Forward and stride-1 data gradient
+// share it (ConvGeom tap list + packed weights).  Wave tile 64 pixels (4 output rows) x 64 channels; waves = TH/4 x BN/64.
 #include "conv_dev.h"
 
 namespace {
@@ -31,19 +31,13 @@ __global__ __launch_bounds__((TH / 4) * (BN / 64) * 64) void k_conv_halo(GeomDev
     __shared__ __attribute__((aligned(16))) T wl[2][BN][LDSROW];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_m = tile / ntile_n, tile_n = tile - tile_m * ntile_n;
-    const int per_img = tiles_h * tiles_w;
-    const int n = tile_m / per_img, trem = tile_m - n * per_img;
-    const int ty = trem / tiles_w, tx = trem - ty * tiles_w;
-    const int y0 = ty * TH, x0 = tx * 16;
-    const int cd0 = tile_n * BN;
+    const BlockTile bt = block_tile<TH, 16, BN>(tiles_h, tiles_w, ntile_n);
+    const int n = bt.n, y0 = bt.y0, x0 = bt.x0, cd0 = bt.cd0;
 
     // ---- loaders (buffer descriptors: fixed per-lane byte offset, scalar per-step offset, out-of-range = 0)
     const int shift = (g.Ws + 1) * g.lds;
-    const __amdgpu_buffer_rsrc_t rsa =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, (g.N * g.Hs * g.Ws * g.lds + shift) * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.e.Cd * g.Kpad * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, (g.N * g.Hs * g.Ws * g.lds + shift) * 2, BUF_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.e.Cd * g.Kpad * 2, BUF_FLAGS);
     int hvoff[HR], hlds[HR];
 #pragma unroll
     for (int r = 0; r < HR; ++r) {
@@ -51,7 +45,7 @@ __global__ __launch_bounds__((TH / 4) * (BN / 64) * 64) void k_conv_halo(GeomDev
         const int px = h >> 2, ck = h & 3;
         const int hy = px / HW, hx = px - hy * HW;
         const bool ok = h < HPX * 4 && (unsigned)(y0 - 1 + hy) < (unsigned)g.Hs && (unsigned)(x0 - 1 + hx) < (unsigned)g.Ws;
-        hvoff[r] = ok ? ((hy * g.Ws + hx) * g.lds + ck * 8) * 2 : (int)0x80000000;
+        hvoff[r] = ok ? ((hy * g.Ws + hx) * g.lds + ck * 8) * 2 : BUF_OOB;
         hlds[r] = h < HPX * 4 ? px * HROW + ck * 8 : -1;
     }
     // scalar origin of the patch: pixel (n, y0-1, x0-1) relative to the shifted descriptor base (never negative)
@@ -62,7 +56,7 @@ __global__ __launch_bounds__((TH / 4) * (BN / 64) * 64) void k_conv_halo(GeomDev
 #pragma unroll
     for (int i = 0; i < WR; ++i) {
         const int row = wrow0 + i * (NTHR / 4);
-        wvoff[i] = (cd0 + row < g.e.Cd) ? ((cd0 + row) * g.Kpad + kseg * 8) * 2 : (int)0x80000000;
+        wvoff[i] = (cd0 + row < g.e.Cd) ? ((cd0 + row) * g.Kpad + kseg * 8) * 2 : BUF_OOB;
     }
 
     uint4 rh[HR], rw[WR];

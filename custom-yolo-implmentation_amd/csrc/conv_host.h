@@ -31,6 +31,11 @@ ConvChoice conv_select(const ConvGeom* gs, int n, int cls, int dtype, const void
 ConvTune& conv_tune();
 int conv_wide_flag();            // conv_mfma.hip: 16-byte epilogue stores: 2 (default) exchange by v_permlane16_swap, 1 by ds_bpermute, 0 off (YOLO_CONV_WIDE, yolo_conv_wide_set)
 
+// ---- the addressing contract of the buffer descriptors: 32-bit byte counts and offsets over 2-byte elements, int pixel indices.
+// elems = all that ONE descriptor covers (a tensor plus the row + pixel its base is shifted back by; a whole weight buffer)
+static inline bool desc_addressable(long elems) { return elems < (1L << 30); }
+static inline bool pixels_addressable(long npix) { return npix < (1L << 31); }
+
 // ---- what the MFMA families share (conv_select.hip): 16-bit dtype, 8-channel source rows, 32-bit byte offsets / buffer
 // descriptors in the gather, 32-bit pixel indices, 16-byte aligned operands, taps within one pixel of the centre
 int mfma_conv_addressable(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst);

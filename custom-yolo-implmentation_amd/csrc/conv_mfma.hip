@@ -41,11 +41,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     __shared__ __attribute__((aligned(16))) T lds_b[2][BN][LDSROW];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nwg = gridDim.x;
-    const int tile = xcd_remap(blockIdx.x, nwg);
-    const int tile_m = tile / ntile_n, tile_n = tile - tile_m * ntile_n;
-    const int m0 = tile_m * BM;
-    const int cd0 = tile_n * BN;
+    const LinearTile lt = linear_tile(ntile_n);
+    const int m0 = lt.tile_m * BM;
+    const int cd0 = lt.tile_n * BN;
     const int total_pix = g.N * g.Hg * g.Wg;
 
     // ---- loader state: two activation rows (r, r+64) and up to two weight rows per thread, fixed k-segment
@@ -94,9 +92,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         }
         // descriptor base = src - one row - one pixel, so the scalar tap offset (dh+1, dw+1) is never negative
         const int shift = (g.Ws + 1) * g.lds;
-        rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, (g.N * g.Hs * g.Ws * g.lds + shift) * 2,
-                                                0x00020000);
-        rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.e.Cd * g.Kpad * 2, 0x00020000);
+        rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, (g.N * g.Hs * g.Ws * g.lds + shift) * 2, BUF_FLAGS);
+        rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, g.e.Cd * g.Kpad * 2, BUF_FLAGS);
         // register staging: this thread loads chunk kseg and stores it at the swizzled slot; LDS-DMA: the lane's
         // slot is fixed (lane-linear image), so it loads the chunk that belongs there
         const int kload = MODE == 3 ? (kseg ^ ((-(lrow >> 2)) & 3)) : kseg;
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         for (int i = 0; i < 2; ++i) voffa[i] = (rowoff[i] + kload * 8) * 2;
 #pragma unroll
         for (int i = 0; i < WR; ++i)
-            voffb[i] = wvalid[i] ? ((cd0 + lrow + i * 64) * g.Kpad + kload * 8) * 2 : (int)0x80000000;
+            voffb[i] = wvalid[i] ? ((cd0 + lrow + i * 64) * g.Kpad + kload * 8) * 2 : BUF_OOB;
     } else {
 #pragma unroll
         for (int i = 0; i < WR; ++i) wrow[i] = wm + (long)(cd0 + (wvalid[i] ? lrow + i * 64 : 0)) * g.Kpad + kseg * 8;
@@ -116,7 +113,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
             const int soff = ((int)((g.dh_pack >> (2 * tap)) & 3u) * g.Ws + (int)((g.dw_pack >> (2 * tap)) & 3u)) * g.lds + cbase;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int vo = ((vmask[i] >> tap) & 1u) ? voffa[i] : (int)0x80000000;
+                const int vo = ((vmask[i] >> tap) & 1u) ? voffa[i] : BUF_OOB;
                 const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsa, vo, soff * 2, 0);
                 ra[i] = make_uint4(v.x, v.y, v.z, v.w);
             }
@@ -159,7 +156,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const int soff = ((int)((g.dh_pack >> (2 * tap)) & 3u) * g.Ws + (int)((g.dw_pack >> (2 * tap)) & 3u)) * g.lds + cbase;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int vo = ((vmask[i] >> tap) & 1u) ? voffa[i] : (int)0x80000000;
+            const int vo = ((vmask[i] >> tap) & 1u) ? voffa[i] : BUF_OOB;
             lds_dma16(rsa, &lds_a[buf][wave * 16 + i * 64][0], vo, soff * 2);
         }
 #pragma unroll
@@ -397,8 +394,8 @@ int mfma_conv_addressable(const ConvGeom& g, int dtype, const void* src, const v
     if (dtype != YOLO_BF16 && dtype != YOLO_F16) return 0;
     if (g.lds % 8 || g.Cd % 8 || g.ldd % 4) return 0;
     // 32-bit byte offsets / buffer descriptors in the gather, 32-bit pixel indices
-    if ((long)g.N * g.Hs * g.Ws * g.lds + (long)(g.Ws + 1) * g.lds >= (1L << 30)) return 0;
-    if ((long)g.N * g.Hg * g.Wg + 256 >= (1L << 31)) return 0;
+    if (!desc_addressable((long)g.N * g.Hs * g.Ws * g.lds + (long)(g.Ws + 1) * g.lds)) return 0;
+    if (!pixels_addressable((long)g.N * g.Hg * g.Wg + 256)) return 0;       // up to the end of the last pixel tile
     if (!al16(src) || !al16(wm) || (reinterpret_cast<uintptr_t>(dst) & 7)) return 0;
     for (int t = 0; t < g.ntaps; ++t)
         if (g.dh[t] < -1 || g.dh[t] > 1 || g.dw[t] < -1 || g.dw[t] > 1) return 0;
@@ -407,7 +404,7 @@ int mfma_conv_addressable(const ConvGeom& g, int dtype, const void* src, const v
 
 // Shapes with an MFMA kernel at all (the gather kernel takes every one of them; which family runs: conv_select.hip)
 int mfma_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst) {
-    return mfma_conv_addressable(g, dtype, src, wm, dst) && g.Cs % 8 == 0 && (long)g.Cd * g.Kpad < (1L << 30);
+    return mfma_conv_addressable(g, dtype, src, wm, dst) && g.Cs % 8 == 0 && desc_addressable((long)g.Cd * g.Kpad);
 }
 
 // the gather kernel with a bn-channel tile (32 / 64 / 128)

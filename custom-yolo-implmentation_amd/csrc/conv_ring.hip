@@ -5,13 +5,14 @@
 // front of the first ds_read of every step -- inside one workgroup nothing overlaps, and layers with one workgroup per
 // CU or fewer (every 20x20 / 40x40 map of the model) run at one L2 round trip per 32-deep K-step.  Here:
 //   * K-steps of 64 elements (two MFMA k-blocks per barrier, LDS rows of 128 bytes = one full cache line per pixel row
-//     and step, the eight 16-byte chunks of a row XOR-swizzled by (row >> 1) & 7) or of 32 elements (64-byte rows,
-//     k_conv_mfma's swizzle): conflict-free ds_read_b128 fragment reads; the swizzle is applied to the lane's SOURCE
-//     chunk, the LDS-DMA image is lane-linear;
+//     and step, the eight 16-byte chunks of a row XOR-swizzled by (row >> 1) & 7) or of 32 elements (the 64-byte-row
+//     image, LDSROW in conv_dev.h): conflict-free ds_read_b128 fragment reads; the swizzle (lds_swz, conv_stage.h) is
+//     applied to the lane's SOURCE chunk, the LDS-DMA image is lane-linear;
 //   * a ring of NST stages filled by LDS-DMA issued from inline asm (invisible to hipcc's wait insertion) and retired
-//     by a COUNTED `s_waitcnt vmcnt((NST-2) * loads per stage)` + one raw s_barrier per step: NST-1 steps of loads
+//     by a COUNTED wait for all but (NST-2) * loads per stage + one raw s_barrier per step: NST-1 steps of loads
 //     stay in flight across barriers.  Stages past the end of K are issued with out-of-range offsets (the hardware
-//     writes zeros, no memory traffic), so the count is the same in every iteration;
+//     writes zeros, no memory traffic), so the count is the same in every iteration.  This is the ring idiom; its one
+//     copy -- lds_dma_piece, dma_wait and the hazards they carry -- is conv_stage.h;
 //   * both operands through buffer descriptors as in k_conv_mfma: fixed per-lane byte offset, one scalar offset per
 //     step (tap, channel chunk), padding taps / rows past the end / partial channel chunks = offset out of range = 0;
 //   * up to four sub-problems per launch (the four parity classes of a stride-2 data gradient: own tap list, weight
@@ -32,27 +33,7 @@ struct RingGeom {
     RingSub sub[4];
 };
 
-// one LDS-DMA piece: 64 lanes x 16 bytes from the descriptor (voffset per lane + scalar offset) to LDS at lds_addr + 16*lane
-__device__ __forceinline__ void ring_dma(__amdgpu_buffer_rsrc_t rs, unsigned lds_addr, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-
-// The counted wait in front of a step's barrier ALSO waits for this wave's own LDS reads (lgkmcnt(0)): the barrier declares the
-// stage read in the previous step free, and hipcc software-pipelines fragment reads across a raw s_barrier (the reads are issued
-// before it, their s_waitcnt lgkmcnt comes after it).  A refill that has to fetch from memory arrives long after such a read has
-// executed; the zero-size-descriptor pieces issued "past the end of K" fetch nothing and can land first -- the read then returns
-// zeros: one (chunk, tap) product missing from a whole workgroup tile, sporadically (found in k_dgrad2_patch, round 3: DESIGN
-// section 6; tools/dbg_up2.py).
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(N) : "memory"); }
-
-// RB = bytes per LDS row = bytes of K per step: 128 (64-deep steps, 8 rows per piece, chunk swizzle (row >> 1) & 7) or
-// 64 (32-deep steps, 16 rows per piece, the swizzle of k_conv_mfma: (-(row >> 2)) & 3)
-template <int RB> __device__ __forceinline__ int ring_swz(int row) {
-    if constexpr (RB == 128) return (row >> 1) & 7;
-    else return (-(row >> 2)) & 3;
-}
-
+// RB = bytes per LDS row = bytes of K per step: 128 (64-deep steps, 8 rows per piece) or 64 (32-deep steps, 16 rows per piece)
 template <typename T, int RB, int WGM, int WGN, int WM, int WN, int NST, bool ACC>
 __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restrict__ src, const T* __restrict__ wm,
                                                    const float* __restrict__ bias, T* __restrict__ dst) {
@@ -63,7 +44,6 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
     static_assert(LA >= 1 && LB >= 1 && BM_ % (4 * RPP) == 0 && BN % (4 * RPP) == 0, "tile shape");
     constexpr int L = LA + LB;
     constexpr int A_BYTES = BM_ * RB, STAGE = (BM_ + BN) * RB;
-    constexpr int OOB = (int)0x80000000;
     using ops = mfma_ops<T>;
     using frag = typename ops::frag;
     __shared__ __attribute__((aligned(1024))) char smem[NST * STAGE];
@@ -91,14 +71,14 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
         const int row = wave * (BM_ / 4) + i * RPP + rp;
-        const int chunk = slot ^ ring_swz<RB>(row);
+        const int chunk = slot ^ lds_swz<RB>(row);
         const int q = m0 + row;
         const bool rv = q < sb.npix;
         const unsigned qq = rv ? q : 0;
         const unsigned t2 = qq / (unsigned)sb.Wg, b = qq - t2 * sb.Wg;
         const unsigned n = t2 / (unsigned)sb.Hg, a = t2 - n * sb.Hg;
         const int hs0 = (int)a * g.sstride, ws0 = (int)b * g.sstride;
-        voffa[i] = rv ? ((((int)n * g.Hs + hs0) * g.Ws + ws0) * g.lds + chunk * 8) * 2 : OOB;
+        voffa[i] = rv ? ((((int)n * g.Hs + hs0) * g.Ws + ws0) * g.lds + chunk * 8) * 2 : BUF_OOB;
         unsigned m = 0;
         for (int t = 0; t < sb.ntaps; ++t) {
             const int dh = (int)((sb.dh_pack >> (2 * t)) & 3u) - 1, dw = (int)((sb.dw_pack >> (2 * t)) & 3u) - 1;
@@ -111,8 +91,8 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
         const int row = wave * (BN / 4) + j * RPP + rp;
-        const int chunk = slot ^ ring_swz<RB>(row);
-        voffb[j] = (cd0 + row < g.e.Cd) ? (sb.wm_off + (cd0 + row) * sb.Kpad + chunk * 8) * 2 : OOB;
+        const int chunk = slot ^ lds_swz<RB>(row);
+        voffb[j] = (cd0 + row < g.e.Cd) ? (sb.wm_off + (cd0 + row) * sb.Kpad + chunk * 8) * 2 : BUF_OOB;
         tailok |= (tail_c0 + chunk * 8 < g.Cs ? 1u : 0u) << (8 + j);
     }
     // descriptor base = src - one row - one pixel, so the scalar tap offset (dh+1, dw+1) is never negative
@@ -124,11 +104,9 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
 
     int tap = 0, cstep = 0, issued = 0, wbuf = 0;             // uniform: the step the next issue() fetches
     auto issue = [&]() {
-        // steps past the end of K go out through descriptors of zero records: every lane is out of range, LDS gets
-        // zeros, nothing is fetched -- and every iteration issues the same number of pieces
-        const bool live = issued < sb.KT;
-        const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, live ? a_bytes : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, live ? w_bytes : 0, 0x00020000);
+        const bool live = issued < sb.KT;                     // past the end of K: zero records, nothing fetched, same piece count
+        const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, live ? a_bytes : 0, BUF_FLAGS);
+        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, live ? w_bytes : 0, BUF_FLAGS);
         const int t = live ? tap : 0;
         const int soffa = (((int)((sb.dh_pack >> (2 * t)) & 3u) * g.Ws + (int)((sb.dw_pack >> (2 * t)) & 3u)) * g.lds + cstep * KE) * 2;
         const int soffb = (t * g.Cs + cstep * KE) * 2;
@@ -138,21 +116,21 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
 #pragma unroll
             for (int i = 0; i < LA; ++i) {
                 const bool ok = ((vmask[i] >> t) & 1u) && ((tailok >> i) & 1u);
-                ring_dma(rsa, base + i * 1024, ok ? voffa[i] : OOB, soffa);
+                lds_dma_piece(rsa, base + i * 1024, ok ? voffa[i] : BUF_OOB, soffa);
             }
 #pragma unroll
-            for (int j = 0; j < LB; ++j) ring_dma(rsb, baseb + j * 1024, ((tailok >> (8 + j)) & 1u) ? voffb[j] : OOB, soffb);
+            for (int j = 0; j < LB; ++j) lds_dma_piece(rsb, baseb + j * 1024, ((tailok >> (8 + j)) & 1u) ? voffb[j] : BUF_OOB, soffb);
         } else if (taps) {
             const unsigned bit = 1u << t;
 #pragma unroll
-            for (int i = 0; i < LA; ++i) ring_dma(rsa, base + i * 1024, (vmask[i] & bit) ? voffa[i] : OOB, soffa);
+            for (int i = 0; i < LA; ++i) lds_dma_piece(rsa, base + i * 1024, (vmask[i] & bit) ? voffa[i] : BUF_OOB, soffa);
 #pragma unroll
-            for (int j = 0; j < LB; ++j) ring_dma(rsb, baseb + j * 1024, voffb[j], soffb);
+            for (int j = 0; j < LB; ++j) lds_dma_piece(rsb, baseb + j * 1024, voffb[j], soffb);
         } else {
 #pragma unroll
-            for (int i = 0; i < LA; ++i) ring_dma(rsa, base + i * 1024, voffa[i], soffa);
+            for (int i = 0; i < LA; ++i) lds_dma_piece(rsa, base + i * 1024, voffa[i], soffa);
 #pragma unroll
-            for (int j = 0; j < LB; ++j) ring_dma(rsb, baseb + j * 1024, voffb[j], soffb);
+            for (int j = 0; j < LB; ++j) lds_dma_piece(rsb, baseb + j * 1024, voffb[j], soffb);
         }
         ++issued;
         if (++cstep == spt) { cstep = 0; ++tap; }
@@ -163,7 +141,7 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
     const int wgm = wave / WGN, wgn = wave - wgm * WGN;
     const int prow = wgm * WM * 16, crow = wgn * WN * 16;
     const int fr = lane & 15, fg = lane >> 4;
-    const int fsw = ring_swz<RB>(fr);                         // swizzle of this lane's fragment rows (row bases are multiples of 16)
+    const int fsw = lds_swz<RB>(fr);                         // swizzle of this lane's fragment rows (row bases are multiples of 16)
     const int foff0 = fr * RB + ((fg ^ fsw) * 16), foff1 = fr * RB + (((4 + fg) ^ fsw) * 16);
     f32x4 acc[WM][WN];
 #pragma unroll
@@ -175,7 +153,7 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
     for (int s = 0; s < NST - 1; ++s) issue();
     int rbuf = 0;
     for (int kt = 0; kt < sb.KT; ++kt) {
-        wait_vmcnt<(NST - 2) * L>();                          // this wave's pieces of stage kt have landed ...
+        dma_wait<(NST - 2) * L>();                            // this wave's pieces of stage kt have landed ...
         __builtin_amdgcn_s_barrier();                         // ... and so have everyone else's; stage kt-1 is free again
         issue();                                              // refill the stage read in the previous step
         const char* sa = smem + rbuf * STAGE + prow * RB;
@@ -195,7 +173,7 @@ __global__ __launch_bounds__(256) void k_conv_ring(RingGeom g, const T* __restri
         }
         if (++rbuf == NST) rbuf = 0;
     }
-    wait_vmcnt<0>();                                          // the zero-fill pieces issued past the end of K
+    dma_wait<0>();                                            // the zero-fill pieces issued past the end of K
 
     // ---- epilogue: lane holds channels c..c+3 of pixel (tile pixel prow + i*16 + fr)
     const int cq = fg * 4;
@@ -254,9 +232,11 @@ int launch_ring(const RingGeom& g, const RingTile& t, int nwg, const void* src, 
 }  // namespace
 
 // Shapes the ring kernel can run (where it is USED: conv_select.hip): what the MFMA families share, source channels a
-// multiple of 32 and at least 64, and a weight matrix the kernel's byte offsets reach with room for its four sub-problems.
+// multiple of 32 and at least 64, and a weight matrix the kernel's byte offsets reach.  The factor 4: one launch may carry
+// the four parity classes of a stride-2 data gradient, whose matrices lie in ONE buffer under one descriptor (wm_off), and
+// together they are no larger than four times this one.
 int ring_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void* wm, const void* dst) {
-    return mfma_conv_addressable(g, dtype, src, wm, dst) && g.Cs % 32 == 0 && g.Cs >= 64 && (long)g.Cd * g.Kpad * 4 < (1L << 30);
+    return mfma_conv_addressable(g, dtype, src, wm, dst) && g.Cs % 32 == 0 && g.Cs >= 64 && desc_addressable((long)g.Cd * g.Kpad * 4);
 }
 
 // gs[0..n): sub-problems that share source, destination tensor, channel counts and strides (n = 1, or the four parity
@@ -264,7 +244,7 @@ int ring_conv_eligible(const ConvGeom& g, int dtype, const void* src, const void
 // weight matrix inside wm, wm_elems = size of the whole buffer
 int ring_conv_launch(const ConvGeom* gs, int n, const RingTile& t, const long* wm_off, long wm_elems, const void* src,
                      const void* wm, const float* bias, void* dst, int accumulate, int dtype, hipStream_t st) {
-    if (n < 1 || n > 4 || wm_elems >= (1L << 30)) return YOLO_ERR_ARG;
+    if (n < 1 || n > 4 || !desc_addressable(wm_elems)) return YOLO_ERR_ARG;
     const ConvGeom& g0 = gs[0];
     RingGeom d;
     d.N = g0.N; d.Hs = g0.Hs; d.Ws = g0.Ws; d.Cs = g0.Cs; d.lds = g0.lds; d.Hd = g0.Hd; d.Wd = g0.Wd;

@@ -8,29 +8,16 @@
 //     pixel order -- a tile may wrap from one row into the next, a lane's pixel only fixes its offset into the staged
 //     patch and the taps stay nine scalar offsets;
 //   * per 32-channel chunk the (rows + 2) x (W + 2) halo patch is staged ONCE, by LDS-DMA, two chunks deep (64-byte
-//     pixel rows, the four 16-byte chunks XOR-swizzled by (pixel >> 1) & 3, patch rows W + 8 pixels apart: conflict-free for ds_read_b128's
-//     lane groups at any pixel offset, also where a tile wraps into the next row);
+//     pixel rows, the four 16-byte chunks XOR-swizzled by (pixel >> 1) & 3, patch rows W + 8 pixels apart: conflict-free for
+//     ds_read_b128's lane groups at any pixel offset, also where a tile wraps into the next row);
 //   * the four waves split the OUTPUT CHANNELS (16 or 32 each) and share the five pixel tiles, so the weight tile of a
 //     step -- one kernel row = three taps x BN x 32 -- is the only per-step traffic; it runs through a ring of NST stages
-//     filled by LDS-DMA and retired by counted s_waitcnt (the idiom of conv_ring.hip): NST-1 steps of weights plus the
+//     filled by LDS-DMA and retired by counted waits (the ring idiom of conv_stage.h): NST-1 steps of weights plus the
 //     next chunk's patch stay in flight across the step barriers.
 // BatchNorm statistics, bias and the accumulate sources in the epilogue as in the other conv kernels.
 #include "conv_dev.h"
-#include <type_traits>
 
 namespace {
-
-__device__ __forceinline__ void rows_dma(__amdgpu_buffer_rsrc_t rs, unsigned lds_addr, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-// The counted wait in front of a step's barrier ALSO waits for this wave's own LDS reads (lgkmcnt(0)): the barrier declares the
-// stage read in the previous step free, and hipcc software-pipelines fragment reads across a raw s_barrier (the reads are issued
-// before it, their s_waitcnt lgkmcnt comes after it).  A refill that has to fetch from memory arrives long after such a read has
-// executed; the zero-size-descriptor pieces issued "past the end of K" fetch nothing and can land first -- the read then returns
-// zeros: one (chunk, tap) product missing from a whole workgroup tile, sporadically (found in k_dgrad2_patch, round 3: DESIGN
-// section 6; tools/dbg_up2.py).
-template <int N> __device__ __forceinline__ void rows_wait() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(N) : "memory"); }
 
 template <typename T, int W, int WGM, int NWAVE, int WN, int NST, bool ACC>
 __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __restrict__ src, const T* __restrict__ wm,
@@ -44,7 +31,6 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
     constexpr int HP = ((HPX + 15) / 16 + NWAVE - 1) / NWAVE; // patch pieces (16 pixels x 64 bytes) per wave
     constexpr int DW = (3 * BN / 16 + NWAVE - 1) / NWAVE;    // weight pieces (16 rows x 64 bytes) per wave and step: 3 taps x BN rows (+ idle pieces)
     constexpr int HBUF = NWAVE * HP * 1024, STAGE = NWAVE * DW * 1024;     // bytes: one patch buffer, one weight stage
-    constexpr int OOB = (int)0x80000000;
     static_assert(R * W == WGM * 80 && NST >= 3 && NST <= 4 && NWAVE == 4, "block shape");
     using ops = mfma_ops<T>;
     using frag = typename ops::frag;
@@ -52,13 +38,8 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)rows_smem);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_m = tile / ntile_n, tile_n = tile - tile_m * ntile_n;
-    const int per_img = tiles_h * tiles_w;
-    const int n = tile_m / per_img, trem = tile_m - n * per_img;
-    const int ty = trem / tiles_w, tx = trem - ty * tiles_w;
-    const int y0 = ty * R, x0 = tx * W;
-    const int cd0 = tile_n * BN;
+    const BlockTile bt = block_tile<R, W, BN>(tiles_h, tiles_w, ntile_n);
+    const int n = bt.n, y0 = bt.y0, x0 = bt.x0, cd0 = bt.cd0;
 
     // ---- DMA sources: fixed per-lane byte offsets (swizzle applied to the SOURCE chunk, the LDS image is lane-linear),
     // one scalar offset per chunk / step, out of range = zeros
@@ -66,11 +47,11 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
     const int a_bytes = (g.N * g.Hs * g.Ws * g.lds + shift) * 2, w_bytes = g.e.Cd * g.Kpad * 2;
     int hvoff[HP], wvoff[DW];
 #pragma unroll
-    for (int i = 0; i < HP; ++i) {
+    for (int i = 0; i < HP; ++i) {                           // patch pieces: piece -> pixel -> swizzled source chunk -> offset
         const int px = (wave * HP + i) * 16 + (lane >> 2), ck = (lane & 3) ^ ((px >> 1) & 3);
         const int hy = px / HWID, hx = px - hy * HWID;
         const bool ok = px < HPX && (unsigned)(y0 - 1 + hy) < (unsigned)g.Hs && (unsigned)(x0 + hx - 1) < (unsigned)g.Ws;
-        hvoff[i] = (ok && ck * 8 < g.Cs) ? ((hy * g.Ws + hx) * g.lds + ck * 8) * 2 : OOB;      // ck*8 >= Cs: a 16-channel source fills half a chunk
+        hvoff[i] = (ok && ck * 8 < g.Cs) ? ((hy * g.Ws + hx) * g.lds + ck * 8) * 2 : BUF_OOB;      // ck*8 >= Cs: a 16-channel source fills half a chunk
     }
     // scalar origin of the patch: pixel (n, y0-1, -1) relative to the shifted descriptor base (never negative)
     const int hsoff0 = (((n * g.Hs + y0 - 1) * g.Ws + x0 - 1) * g.lds + shift) * 2;
@@ -78,24 +59,23 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
     for (int j = 0; j < DW; ++j) {
         const int rs = (wave * DW + j) * 16 + (lane >> 2);   // row of the stage: (tap of the step, channel)
         const int tl = rs / BN, row = rs - tl * BN;
-        const int kseg = (lane & 3) ^ ((-(row >> 2)) & 3);   // k_conv_mfma's swizzle
-        wvoff[j] = (tl < 3 && cd0 + row < g.e.Cd && kseg * 8 < g.Cs) ? ((cd0 + row) * g.Kpad + tl * g.Cs + kseg * 8) * 2 : OOB;
+        const int kseg = (lane & 3) ^ ((-(row >> 2)) & 3);   // the 64-byte-row image (LDSROW)
+        wvoff[j] = (tl < 3 && cd0 + row < g.e.Cd && kseg * 8 < g.Cs) ? ((cd0 + row) * g.Kpad + tl * g.Cs + kseg * 8) * 2 : BUF_OOB;
     }
     const int nchunk = (g.Cs + BK - 1) / BK, nit = nchunk * 3;   // Cs is a multiple of 32, or 16 (one half-filled chunk)
     auto issue_halo = [&](int chunk) {                       // chunks past the end: zero-size descriptor, same piece count
-        const __amdgpu_buffer_rsrc_t rsa =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, chunk < nchunk ? a_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src) - shift, 0, chunk < nchunk ? a_bytes : 0, BUF_FLAGS);
         const unsigned base = lds0 + (chunk & 1) * HBUF + wave * (HP * 1024);
 #pragma unroll
-        for (int i = 0; i < HP; ++i) rows_dma(rsa, base + i * 1024, hvoff[i], hsoff0 + chunk * 64);
+        for (int i = 0; i < HP; ++i) lds_dma_piece(rsa, base + i * 1024, hvoff[i], hsoff0 + chunk * 64);
     };
     int wstep = 0, wchunk = 0, wrow = 0, wbuf = 0;           // uniform: the step the next issue_w() fetches
     auto issue_w = [&]() {
-        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, wstep < nit ? w_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, wstep < nit ? w_bytes : 0, BUF_FLAGS);
         const unsigned base = lds0 + 2 * HBUF + wbuf * STAGE + wave * (DW * 1024);
         const int soff = (3 * wrow * g.Cs + wchunk * BK) * 2;
 #pragma unroll
-        for (int j = 0; j < DW; ++j) rows_dma(rsb, base + j * 1024, wvoff[j], soff);
+        for (int j = 0; j < DW; ++j) lds_dma_piece(rsb, base + j * 1024, wvoff[j], soff);
         ++wstep;
         if (++wrow == 3) { wrow = 0; ++wchunk; }
         if (++wbuf == NST) wbuf = 0;
@@ -133,7 +113,7 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
         constexpr int srow = decltype(srow_c)::value, par = decltype(par_c)::value;   // par: patch buffer of this chunk (static: folds into the read's immediate)
         // newer than this step's weights: NST-2 later steps, and the next patch when it went out in one of those iterations
         constexpr bool patch_newer = srow != 0 && (NST == 4 || srow == 1);
-        rows_wait<(NST - 2) * DW + (patch_newer ? HP : 0)>();
+        dma_wait<(NST - 2) * DW + (patch_newer ? HP : 0)>();
         __builtin_amdgcn_s_barrier();                        // everyone's pieces of this step are in; the stage / patch read last step is free
         if (srow == 0) issue_halo(chunk + 1);
         issue_w();
@@ -155,16 +135,14 @@ __global__ __launch_bounds__(64 * NWAVE) void k_conv_rows(GeomDev g, const T* __
         }
         if (++rbuf == NST) rbuf = 0;
     };
-    using c0 = std::integral_constant<int, 0>;
-    using c1 = std::integral_constant<int, 1>;
-    using c2 = std::integral_constant<int, 2>;
+    using c0 = ic<0>; using c1 = ic<1>; using c2 = ic<2>;
     int chunk = 0;
     for (; chunk + 1 < nchunk; chunk += 2) {
         step(c0{}, c0{}, chunk); step(c1{}, c0{}, chunk); step(c2{}, c0{}, chunk);
         step(c0{}, c1{}, chunk + 1); step(c1{}, c1{}, chunk + 1); step(c2{}, c1{}, chunk + 1);
     }
     if (chunk < nchunk) { step(c0{}, c0{}, chunk); step(c1{}, c0{}, chunk); step(c2{}, c0{}, chunk); }
-    rows_wait<0>();                                          // the zero-fill pieces issued past the end of K
+    dma_wait<0>();                                           // the zero-fill pieces issued past the end of K
     __syncthreads();                                         // LDS is idle from here on (statistics scratch)
 
     // ---- epilogue: lane holds channels c..c+3 of its pixel of tile i
@@ -196,11 +174,8 @@ int launch_rows(const GeomDev& d, const void* src, const void* wm, const float* 
     const int th = (d.Hg + R - 1) / R, tw = W == 16 ? (d.Wg + 15) / 16 : 1, tn = (d.e.Cd + BN - 1) / BN;
     const dim3 grid((unsigned)(d.N * th * tw * tn));
     return with_acc(accumulate, [&](auto acc) {
-        constexpr bool ACC = decltype(acc)::value;
-        static unsigned long long done = 0;         // per instantiation: devices that have the attribute
-        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_conv_rows<T, W, WGM, NWAVE, WN, NST, ACC>), lds, done)) return e;
-        hipLaunchKernelGGL((k_conv_rows<T, W, WGM, NWAVE, WN, NST, ACC>), grid, dim3(64 * NWAVE), lds, st, d, (const T*)src, (const T*)wm, bias, (T*)dst, th, tw, tn);
-        return YOLO_LAUNCH_CHECK();
+        return launch_dyn_lds<k_conv_rows<T, W, WGM, NWAVE, WN, NST, decltype(acc)::value>>(grid, dim3(64 * NWAVE), lds, st, d, (const T*)src,
+                                                                                            (const T*)wm, bias, (T*)dst, th, tw, tn);
     });
 }
 

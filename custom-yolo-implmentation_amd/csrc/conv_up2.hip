@@ -7,13 +7,12 @@
 // rows, chunk-swizzled), the nine (class, tap) products read it at scalar pixel offsets, and each class keeps its own
 // accumulators (wave tile 64 pixels x 32 channels x 4 classes = 128 accumulator registers, two waves per SIMD).  Weights:
 // the four class matrices of yolo_conv_pack_weights(mode 1), three (class, tap) tiles per barrier step through an LDS-DMA
-// ring retired by counted s_waitcnt (the idiom of conv_ring.hip); the next chunk's patch rides the same queue.  The four
+// ring retired by counted waits (the ring idiom of conv_stage.h); the next chunk's patch rides the same queue.  The four
 // classes of a pixel pair leave the same wave back to back, so L2 sees whole dx lines.
 // PMC (128->128 @160x160, profiles/r2_up2_pmc.md): MFMA busy 25 % of the kernel, 59 % of wave time in s_waitcnt -- on the
 // DMA queue, not on LDS (SQ_WAIT_INST_LDS 4 %, bank conflicts 0): 335 MB through HBM / L2 in 107 us, the kernel is
 // memory-side bound like its neighbours; ring depth 3 = depth 4, fragment-read scheduling +-1 %.
 #include "conv_dev.h"
-#include <type_traits>
 
 namespace {
 
@@ -32,18 +31,6 @@ __device__ __forceinline__ constexpr int up2_tap(int p) { return p == 0 ? 0 : p 
 __device__ __forceinline__ constexpr int up2_dh(int p) { return p == 4 || p >= 7 ? 1 : 0; }
 __device__ __forceinline__ constexpr int up2_dw(int p) { return p == 2 || p == 6 || p == 8 ? 1 : 0; }
 
-__device__ __forceinline__ void up2_dma(__amdgpu_buffer_rsrc_t rs, unsigned lds_addr, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-// The counted wait in front of a step's barrier ALSO waits for this wave's own LDS reads (lgkmcnt(0)): the barrier declares the
-// stage read in the previous step free, and hipcc software-pipelines fragment reads across a raw s_barrier (the reads are issued
-// before it, their s_waitcnt lgkmcnt comes after it).  A refill that has to fetch from memory arrives long after such a read has
-// executed; the zero-size-descriptor pieces issued "past the end of K" fetch nothing and can land first -- the read then returns
-// zeros: one (chunk, tap) product missing from a whole workgroup tile, sporadically (found in k_dgrad2_patch, round 3: DESIGN
-// section 6; tools/dbg_up2.py).
-template <int N> __device__ __forceinline__ void up2_wait() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(N) : "memory"); }
-
 template <typename T, int TH, int BN, int WM, int NST, bool ACC>
 __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_waves_per_eu(8 / WM, 8 / WM))) void k_dgrad2_patch(
     Up2Geom g, const T* __restrict__ src, const T* __restrict__ wm, T* __restrict__ dst, int tiles_h, int tiles_w, int ntile_n) {
@@ -52,7 +39,6 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
     constexpr int HP = ((PPX + 15) / 16 + NW - 1) / NW;      // patch pieces (16 pixels x 64 bytes) per wave and chunk
     constexpr int DW = (3 * BN / 16 + NW - 1) / NW;          // weight pieces (16 rows x 64 bytes) per wave and step: 3 tiles x BN rows
     constexpr int HBUF = NW * HP * 1024, STAGE = NW * DW * 1024;      // bytes: one patch buffer, one weight stage
-    constexpr int OOB = (int)0x80000000;
     static_assert(NST == 3 || NST == 4, "ring depth");
     using ops = mfma_ops<T>;
     using frag = typename ops::frag;
@@ -60,25 +46,20 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)up2_smem);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_m = tile / ntile_n, tile_n = tile - tile_m * ntile_n;
-    const int per_img = tiles_h * tiles_w;
-    const int n = tile_m / per_img, trem = tile_m - n * per_img;
-    const int ty = trem / tiles_w, tx = trem - ty * tiles_w;
-    const int y0 = ty * TH, x0 = tx * 16;
-    const int cd0 = tile_n * BN;
+    const BlockTile bt = block_tile<TH, 16, BN>(tiles_h, tiles_w, ntile_n);
+    const int n = bt.n, y0 = bt.y0, x0 = bt.x0, cd0 = bt.cd0;
 
     // ---- DMA sources: fixed per-lane byte offsets (swizzle applied to the SOURCE chunk, the LDS image is lane-linear),
     // one scalar offset per chunk, out of range = zeros.  Patch rows: 64 bytes, chunk ^ ((pixel >> 1) & 3) -- conflict-free for
-    // ds_read_b128's lane groups at any pixel offset; weight rows: k_conv_mfma's swizzle.
+    // ds_read_b128's lane groups at any pixel offset; weight rows: the 64-byte-row image (LDSROW, conv_dev.h).
     const int a_bytes = g.N * g.Hs * g.Ws * g.lds * 2, w_bytes = g.wm_elems * 2;
     int hvoff[HP], wvoff[3][DW];
 #pragma unroll
-    for (int i = 0; i < HP; ++i) {
+    for (int i = 0; i < HP; ++i) {                           // patch pieces: piece -> pixel -> swizzled source chunk -> offset
         const int px = (wave * HP + i) * 16 + (lane >> 2), ck = (lane & 3) ^ ((px >> 1) & 3);
         const int hy = px / UPW, hx = px - hy * UPW;
         const bool ok = px < PPX && y0 + hy < g.Hs && x0 + hx < g.Ws;
-        hvoff[i] = ok ? ((hy * g.Ws + hx) * g.lds + ck * 8) * 2 : OOB;
+        hvoff[i] = ok ? ((hy * g.Ws + hx) * g.lds + ck * 8) * 2 : BUF_OOB;
     }
     const int hsoff0 = ((n * g.Hs + y0) * g.Ws + x0) * g.lds * 2;
 #pragma unroll
@@ -94,23 +75,23 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
             const int t = p == 0 ? 0 : p < 3 ? p - 1 : p < 5 ? p - 3 : p - 5;
             const int off = c == 0 ? g.wm_off[0] : c == 1 ? g.wm_off[1] : c == 2 ? g.wm_off[2] : g.wm_off[3];   // no dynamic kernarg indexing
             const int kp = c == 0 ? g.Kpad[0] : c == 1 ? g.Kpad[1] : c == 2 ? g.Kpad[2] : g.Kpad[3];
-            wvoff[s][j] = ok ? (off + (cd0 + row) * kp + t * g.Cs + kseg * 8) * 2 : OOB;
+            wvoff[s][j] = ok ? (off + (cd0 + row) * kp + t * g.Cs + kseg * 8) * 2 : BUF_OOB;
         }
     }
     const int nchunk = g.Cs / BK;
     auto issue_patch = [&](int chunk) {                      // chunks past the end: zero-size descriptor, same piece count
-        const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src), 0, chunk < nchunk ? a_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src), 0, chunk < nchunk ? a_bytes : 0, BUF_FLAGS);
         const unsigned base = lds0 + (chunk & 1) * HBUF + wave * (HP * 1024);
 #pragma unroll
-        for (int i = 0; i < HP; ++i) up2_dma(rsa, base + i * 1024, hvoff[i], hsoff0 + chunk * 64);
+        for (int i = 0; i < HP; ++i) lds_dma_piece(rsa, base + i * 1024, hvoff[i], hsoff0 + chunk * 64);
     };
     int wchunk = 0, wbuf = 0;                                // uniform: chunk and ring slot of the next weight issue
     auto issue_w = [&](auto s_c) {
         constexpr int s = decltype(s_c)::value;
-        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, wchunk < nchunk ? w_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wm), 0, wchunk < nchunk ? w_bytes : 0, BUF_FLAGS);
         const unsigned base = lds0 + 2 * HBUF + wbuf * STAGE + wave * (DW * 1024);
 #pragma unroll
-        for (int j = 0; j < DW; ++j) up2_dma(rsb, base + j * 1024, wvoff[s][j], wchunk * 64);
+        for (int j = 0; j < DW; ++j) lds_dma_piece(rsb, base + j * 1024, wvoff[s][j], wchunk * 64);
         if (s == 2) ++wchunk;
         if (++wbuf == NST) wbuf = 0;
     };
@@ -133,18 +114,18 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
 
     // prologue: patch 0, then NST-1 weight steps (the issue order of the steady state: step it issues step it+NST-1)
     issue_patch(0);
-    issue_w(std::integral_constant<int, 0>{});
-    issue_w(std::integral_constant<int, 1>{});
-    if (NST == 4) issue_w(std::integral_constant<int, 2>{});
+    issue_w(ic<0>{});
+    issue_w(ic<1>{});
+    if (NST == 4) issue_w(ic<2>{});
     int rbuf = 0;
     auto step = [&](auto s_c, int chunk) {
         constexpr int s = decltype(s_c)::value;
         // newer than this step's weights: NST-2 later steps, and the next patch when it went out in one of those iterations
         constexpr bool patch_newer = s != 0 && (NST == 4 || s == 1);
-        up2_wait<(NST - 2) * DW + (patch_newer ? HP : 0)>();
+        dma_wait<(NST - 2) * DW + (patch_newer ? HP : 0)>();
         __builtin_amdgcn_s_barrier();                        // everyone's pieces of this step are in; last step's stage / patch is free
         if (s == 0) issue_patch(chunk + 1);
-        issue_w(std::integral_constant<int, (s + NST - 1) % 3>{});
+        issue_w(ic<(s + NST - 1) % 3>{});
         const char* hp = up2_smem + (chunk & 1) * HBUF;
         const char* wp = up2_smem + 2 * HBUF + rbuf * STAGE;
         frag fa[3][2], fb[3][WM];
@@ -178,11 +159,11 @@ __global__ __launch_bounds__((TH / WM) * (BN / 32) * 64) __attribute__((amdgpu_w
         if (++rbuf == NST) rbuf = 0;
     };
     for (int chunk = 0; chunk < nchunk; ++chunk) {
-        step(std::integral_constant<int, 0>{}, chunk);
-        step(std::integral_constant<int, 1>{}, chunk);
-        step(std::integral_constant<int, 2>{}, chunk);
+        step(ic<0>{}, chunk);
+        step(ic<1>{}, chunk);
+        step(ic<2>{}, chunk);
     }
-    up2_wait<0>();                                           // the zero-fill pieces issued past the end of K
+    dma_wait<0>();                                           // the zero-fill pieces issued past the end of K
 
     // ---- epilogue: lane holds channels c..c+3 of dy-grid pixel (row wgm*WM+i, col fr); class (ph, pw) -> dx (2a+ph, 2b+pw)
     const int cq = fg * 4;
@@ -210,11 +191,8 @@ int launch_up2(const Up2Geom& d, const void* src, const void* wm, void* dst, int
     const int th = (d.Hs + TH - 1) / TH, tw = (d.Ws + 15) / 16, tn = (d.e.Cd + BN - 1) / BN;
     const dim3 grid((unsigned)(d.N * th * tw * tn));
     return with_acc(accumulate, [&](auto acc) {
-        constexpr bool ACC = decltype(acc)::value;
-        static unsigned long long done = 0;         // per instantiation: devices that have the attribute
-        if (int e = yolo_allow_dyn_lds(reinterpret_cast<const void*>(k_dgrad2_patch<T, TH, BN, WM, NST, ACC>), lds, done)) return e;
-        hipLaunchKernelGGL((k_dgrad2_patch<T, TH, BN, WM, NST, ACC>), grid, dim3(NTHR), lds, st, d, (const T*)src, (const T*)wm, (T*)dst, th, tw, tn);
-        return YOLO_LAUNCH_CHECK();
+        return launch_dyn_lds<k_dgrad2_patch<T, TH, BN, WM, NST, decltype(acc)::value>>(grid, dim3(NTHR), lds, st, d, (const T*)src, (const T*)wm,
+                                                                                        (T*)dst, th, tw, tn);
     });
 }
 
@@ -228,7 +206,7 @@ int up2_conv_eligible(const ConvGeom* gs, int dtype) {
     const ConvGeom& g = gs[0];
     if (dtype != YOLO_BF16 && dtype != YOLO_F16) return 0;
     if ((g.Hd & 1) || (g.Wd & 1) || g.Hs * 2 != g.Hd || g.Ws * 2 != g.Wd || g.Cs % 32 || g.Cd % 8 || g.Cd < 32 || g.lds % 8 || g.ldd % 4) return 0;
-    if ((long)g.N * g.Hs * g.Ws * g.lds >= (1L << 30) || (long)g.N * g.Hd * g.Wd >= (1L << 31)) return 0;
+    if (!desc_addressable((long)g.N * g.Hs * g.Ws * g.lds) || !pixels_addressable((long)g.N * g.Hd * g.Wd)) return 0;
     for (int c = 0; c < 4; ++c) {
         const ConvGeom& q = gs[c];
         if (q.ntaps != want_taps[c] || q.ostep != 2 || q.sstride != 1 || q.ooff_h != (c >> 1) || q.ooff_w != (c & 1) || q.Hg != g.Hs ||
@@ -244,15 +222,13 @@ int up2_conv_eligible(const ConvGeom* gs, int dtype) {
 int up2_conv_launch(const ConvGeom* gs, int variant, const long* wm_off, long wm_elems, const void* src, const void* wm, void* dst,
                     int accumulate, int dtype, hipStream_t st) {
     const ConvGeom& g = gs[0];
-    if (wm_elems >= (1L << 30) || (reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(wm) & 15) ||
+    if (!desc_addressable(wm_elems) || (reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(wm) & 15) ||
         (reinterpret_cast<uintptr_t>(dst) & 7))
         return YOLO_ERR_ARG;
     Up2Geom d;
     d.N = g.N; d.Hs = g.Hs; d.Ws = g.Ws; d.Cs = g.Cs; d.lds = g.lds; d.Hd = g.Hd; d.Wd = g.Wd;
     for (int c = 0; c < 4; ++c) { d.wm_off[c] = (int)wm_off[c]; d.Kpad[c] = gs[c].Kpad; }
     d.wm_elems = (int)wm_elems;
-    // (Round 3: with the 16-byte exchange path this kernel returned a whole workgroup tile of parity class (1,1) short of one
-    // (chunk, tap) product in a few launches of a hundred.  Not the stores: the counted waits of the ring, see up2_wait.)
     d.e = to_epi(g);        // a data gradient: no activation, residual or statistics; up2_conv_eligible refuses a second source
     if (g.N * g.Hs * g.Ws == 0) return YOLO_OK;
 #define UP2_T(T_)                                                                                       \

@@ -56,8 +56,6 @@ struct DwGeom {
     int act;
 };
 
-constexpr int OOB = (int)0x80000000;
-
 // taps of the workgroup's channels -> LDS, [tap][half][cvb][4]
 template <bool FLIP>
 __device__ __forceinline__ void stage_taps(float* wl, const float* __restrict__ w, int c0, int C, int cvb) {
@@ -94,8 +92,7 @@ __global__ __launch_bounds__(256) void k_dw3x3_strip(DwGeom g, const T* __restri
     float ssum[8], ssq[8];                                   // BatchNorm batch statistics of the stored (rounded) values
 #pragma unroll
     for (int j = 0; j < 8; ++j) ssum[j] = ssq[j] = 0.f;
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x), 0, g.N * g.H * g.W * g.ldx * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buf_desc(x, g.N * g.H * g.W * g.ldx * 2);
     const float4* wq = reinterpret_cast<const float4*>(wl) + cgl;
     for (long s = blockIdx.x; active && s < g.total; s += gridDim.x) {
         const int cbk = (int)(s % g.ncb);
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(256) void k_dw3x3_strip(DwGeom g, const T* __restri
             for (int c = 0; c < 3; ++c) {
                 const int ws = wc - 1 + c;
                 const bool ok = rok && (unsigned)ws < (unsigned)g.W;
-                const int off = ok ? ((((n * g.H + hs) * g.W + ws) * g.ldx + ch) * 2) : OOB;
+                const int off = ok ? ((((n * g.H + hs) * g.W + ws) * g.ldx + ch) * 2) : BUF_OOB;
                 v[r][c] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
             }
         }
@@ -205,10 +202,8 @@ __global__ __launch_bounds__(256) void k_dw3x3_wgrad_strip(DwGeom g, const T* __
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[t][j] = 0.f;
-    const __amdgpu_buffer_rsrc_t rsx =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x), 0, g.N * g.H * g.W * g.ldx * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsy =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(dy), 0, g.N * g.H * g.W * g.ldy * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsx = buf_desc(x, g.N * g.H * g.W * g.ldx * 2);
+    const __amdgpu_buffer_rsrc_t rsy = buf_desc(dy, g.N * g.H * g.W * g.ldy * 2);
     if (active) {
         for (long s = blockIdx.x; s < g.total; s += gridDim.x) {
             const int cbk = (int)(s % g.ncb);
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(256) void k_dw3x3_wgrad_strip(DwGeom g, const T* __
 #pragma unroll
             for (int o = 0; o < R; ++o) {
                 const bool ok = h0 + o < g.H;
-                gv[o] = __builtin_amdgcn_raw_buffer_load_b128(rsy, ok ? ((((n * g.H + h0 + o) * g.W + wc) * g.ldy + ch) * 2) : OOB, 0, 0);
+                gv[o] = __builtin_amdgcn_raw_buffer_load_b128(rsy, ok ? ((((n * g.H + h0 + o) * g.W + wc) * g.ldy + ch) * 2) : BUF_OOB, 0, 0);
             }
 #pragma unroll
             for (int r = 0; r < R + 2; ++r) {
@@ -230,7 +225,7 @@ __global__ __launch_bounds__(256) void k_dw3x3_wgrad_strip(DwGeom g, const T* __
                 for (int c = 0; c < 3; ++c) {
                     const int ws = wc - 1 + c;
                     const bool ok = rok && (unsigned)ws < (unsigned)g.W;
-                    v[r][c] = __builtin_amdgcn_raw_buffer_load_b128(rsx, ok ? ((((n * g.H + hs) * g.W + ws) * g.ldx + ch) * 2) : OOB, 0, 0);
+                    v[r][c] = __builtin_amdgcn_raw_buffer_load_b128(rsx, ok ? ((((n * g.H + hs) * g.W + ws) * g.ldx + ch) * 2) : BUF_OOB, 0, 0);
                 }
             }
             float gf[R][8];
@@ -275,24 +270,24 @@ __global__ __launch_bounds__(256) void k_dw3x3_wgrad_strip(DwGeom g, const T* __
 constexpr int DW_PF = 2;                                     // input rows in flight ahead of the row being computed
 constexpr int DW_PF_WGRAD = 1;                               // weight gradient (72 sums per thread): one row less, for its three waves per SIMD
 
-struct DwCols { unsigned off[3]; };                          // byte offset of the thread's three columns inside a row, or OOB
+struct DwCols { unsigned off[3]; };                          // byte offset of the thread's three columns inside a row, or BUF_OOB
 
 __device__ __forceinline__ DwCols dw_cols(int wc, int W, int ld, int ch) {
     DwCols c;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const int ws = wc - 1 + k;
-        c.off[k] = (unsigned)ws < (unsigned)W ? (unsigned)((ws * ld + ch) * 2) : (unsigned)OOB;
+        c.off[k] = (unsigned)ws < (unsigned)W ? (unsigned)((ws * ld + ch) * 2) : (unsigned)BUF_OOB;
     }
     return c;
 }
 
-// One packet of row r of a tensor: the thread's column offset as the vector offset (an OOB column stays out of range), the
+// One packet of row r of a tensor: the thread's column offset as the vector offset (a BUF_OOB column stays out of range), the
 // row's offset as the scalar offset, and a descriptor of NO records for a row the caller rules out (above / below the image,
 // beyond the band): zeros without a fetch, and no address arithmetic per load.
 template <typename T>
 __device__ __forceinline__ u32x4 dw_load(const T* p, int bytes, bool rok, unsigned coloff, unsigned rowoff) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p), 0, rok ? bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buf_desc(p, rok ? bytes : 0);
     return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)coloff, (int)(rok ? rowoff : 0u), 0);
 }
 

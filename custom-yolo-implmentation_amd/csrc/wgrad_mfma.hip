@@ -116,10 +116,8 @@ __global__ __launch_bounds__(256) void k_wgrad2(WgArgs a, const T* __restrict__ 
     // starts one row and one pixel before the tensor so the origin of a border patch is never negative.
     // Patch coordinates (n, bh, bw) advance by carrying -- no division in the loop.  (host: sizes < 2^30 elements)
     const int xshift = (a.W + 1) * a.ldx;
-    const __amdgpu_buffer_rsrc_t rsx =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x) - xshift, 0, (a.N * a.H * a.W * a.ldx + xshift) * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsy =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(dy), 0, a.N * a.OH * a.OW * a.ldy * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsx = buf_desc(x - xshift, (a.N * a.H * a.W * a.ldx + xshift) * 2);
+    const __amdgpu_buffer_rsrc_t rsy = buf_desc(dy, a.N * a.OH * a.OW * a.ldy * 2);
     int yrow[YR], ycol[YR], yvoff[YR], ylds[YR];             // dY chunk: pixel (row, col) of the 4x8 patch + channel chunk
 #pragma unroll
     for (int r = 0; r < YR; ++r) {
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(256) void k_wgrad2(WgArgs a, const T* __restrict__ 
         const int j = id / CPY, ch = (id - j * CPY) * 8;
         yrow[r] = j >> 3;
         ycol[r] = j & 7;
-        yvoff[r] = (id < YCH && bco + ch < a.Cout) ? ((yrow[r] * a.OW + ycol[r]) * a.ldy + bco + ch) * 2 : (int)0x80000000;
+        yvoff[r] = (id < YCH && bco + ch < a.Cout) ? ((yrow[r] * a.OW + ycol[r]) * a.ldy + bco + ch) * 2 : BUF_OOB;
         ylds[r] = id < YCH ? ((j & 3) + 4 * ((j >> 3) & 1) + 8 * ((j >> 2) & 1) + 16 * (j >> 4)) * LDY + ch : -1;
     }
     int xpr[XR], xpc[XR], xvoff[XR], xlds[XR];
@@ -137,7 +135,7 @@ __global__ __launch_bounds__(256) void k_wgrad2(WgArgs a, const T* __restrict__ 
         const int px = id / CPX, ch = (id - px * CPX) * 8;
         xpr[r] = px / PW;
         xpc[r] = px - xpr[r] * PW;
-        xvoff[r] = (id < XCH && bci + ch < a.Cin) ? ((xpr[r] * a.W + xpc[r]) * a.ldx + bci + ch) * 2 : (int)0x80000000;
+        xvoff[r] = (id < XCH && bci + ch < a.Cin) ? ((xpr[r] * a.W + xpc[r]) * a.ldx + bci + ch) * 2 : BUF_OOB;
         const int row = S == 1 ? xpr[r] * PWL + xpc[r]
                                : ((xpr[r] & 1) * 2 + (xpc[r] & 1)) * SUB + (xpr[r] >> 1) * PWL + (xpc[r] >> 1);
         xlds[r] = id < XCH ? row * LDX + ch : -1;
@@ -162,14 +160,14 @@ __global__ __launch_bounds__(256) void k_wgrad2(WgArgs a, const T* __restrict__ 
 #pragma unroll
         for (int r = 0; r < YR; ++r) {
             const bool ok = live && oh0 + yrow[r] < a.OH && ow0 + ycol[r] < a.OW;
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsy, ok ? yvoff[r] : (int)0x80000000, ysoff, 0);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsy, ok ? yvoff[r] : BUF_OOB, ysoff, 0);
             ry_[r] = make_uint4(v.x, v.y, v.z, v.w);
         }
         const int xsoff = live ? (((pn * a.H + ih0) * a.W + iw0) * a.ldx + xshift) * 2 : 0;
 #pragma unroll
         for (int r = 0; r < XR; ++r) {
             const bool ok = live && (unsigned)(ih0 + xpr[r]) < (unsigned)a.H && (unsigned)(iw0 + xpc[r]) < (unsigned)a.W;
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsx, ok ? xvoff[r] : (int)0x80000000, xsoff, 0);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsx, ok ? xvoff[r] : BUF_OOB, xsoff, 0);
             rx_[r] = make_uint4(v.x, v.y, v.z, v.w);
         }
         if (++pbw == a.pbw) {

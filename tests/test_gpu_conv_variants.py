@@ -583,7 +583,7 @@ def test_config2_wide_and_narrow_epilogue_stores_are_bit_identical_on_every_imag
 
 @pytest.mark.parametrize("wide", [1, 2, 0])
 def test_stride2_patch_kernel_repeats_bit_for_bit_on_every_image(wide):
-    """Regression for round 3's ring race (conv_up2.hip: up2_wait): the 128 -> 128 3x3 / 2 data gradient @160x160 at 32 images,
+    """Regression for round 3's ring race (conv_stage.h: dma_wait): the 128 -> 128 3x3 / 2 data gradient @160x160 at 32 images,
     the launch in which whole workgroup tiles used to come out one product short in a few runs of a hundred (with the
     ds_bpermute epilogue, wide = 1, within a dozen).  Twelve launches, every image, each compared bit for bit with the first;
     the first against the 8-byte-store form."""
