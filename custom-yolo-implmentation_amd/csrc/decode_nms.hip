@@ -3,7 +3,7 @@
 //
 // NMS, per image, all on device, deterministic:
 //   k_candidates : confidence filter + best class (or every class above the threshold when
-//                  multi_label), optional class whitelist, xywh->xyxy with each operation rounded in
+//                  multi_label; a NaN class score drops the anchor), optional class whitelist, xywh->xyxy with each operation rounded in
 //                  the input dtype T (the reference does this arithmetic in T before torch.cat promotes
 //                  the rows to fp32); order-preserving compaction by block scans
 //   k_rank       : stable descending order by counting (rank = #better), cap 30000 (max_nms)
@@ -104,7 +104,9 @@ __device__ __forceinline__ int block_excl_scan(int v, int* lds4, int& total) {
     return base + inc - v;
 }
 
-// candidates of anchor m: their number (0 / 1, or the passing classes with multi_label), best class and score
+// candidates of anchor m: their number (0 / 1, or the passing classes with multi_label), best class and score.
+// An anchor with a NaN class score has none, in either mode: the reference's amax(1) > conf_thres (:206) propagates the
+// NaN and the comparison is false.
 template <typename T>
 __device__ __forceinline__ int cand_eval(const T* __restrict__ yi, int m, int M, int nc, int multi_label, float conf_thres,
                                          const ClsFilter& filt, float& best, int& bestc) {
@@ -112,12 +114,15 @@ __device__ __forceinline__ int cand_eval(const T* __restrict__ yi, int m, int M,
     best = -INFINITY;
     bestc = 0;
     if (m < M) {
+        bool nan = false;
         for (int c = 0; c < nc; ++c) {
             float v = to_f<T>(yi[(long)(4 + c) * M + m]);
+            nan |= (v != v);
             if (multi_label) { if (v > conf_thres && cls_ok(filt, c)) ++cnt; }
             else if (v > best) { best = v; bestc = c; }
         }
         if (!multi_label) cnt = (best > conf_thres && cls_ok(filt, bestc)) ? 1 : 0;
+        if (nan) cnt = 0;
     }
     return cnt;
 }
@@ -295,7 +300,7 @@ __global__ __launch_bounds__(64) void k_scan(const float* __restrict__ rows, con
 // ---- validation path: reference src/training/train_model.py:14-142 (decode_predictions) and
 // src/training/metrics.py:68-157 (DetectionMetrics.update) -------------------------------------------------------
 // k_val_candidates : per anchor sigmoid of every class logit rounded in T (the reference applies .sigmoid() to the T
-//                    tensor), first maximum, `>= conf` compared in T; order-preserving compaction
+//                    tensor), first maximum, `>= conf` compared in T, an anchor with a NaN score dropped; order-preserving compaction
 // k_val_rank       : only for images with more survivors than top_k: descending score, lower anchor first on ties
 //                    (torch.topk leaves the order of equal scores unspecified)
 // k_val_gather     : the kept rows [cx, cy, w, h, cls, score] per image
@@ -308,12 +313,14 @@ __device__ __forceinline__ int val_eval(const T* __restrict__ yi, int m, int M, 
     best = -INFINITY;
     bestc = 0;
     if (m >= M) return 0;
+    bool nan = false;                                         // the reference's max(1) propagates a NaN score: the anchor is dropped
     for (int c = 0; c < nc; ++c) {
         const float v = to_f<T>(yi[(long)(4 + c) * M + m]);
         const float sg = rt<T>(1.f / (1.f + expf(-v)));
+        nan |= (sg != sg);
         if (sg > best) { best = sg; bestc = c; }
     }
-    return best >= conf ? 1 : 0;
+    return (!nan && best >= conf) ? 1 : 0;
 }
 
 // two passes over 256-anchor chunks like the NMS candidates (k_cand_count / k_candidates): count, then place each chunk

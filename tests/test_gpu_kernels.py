@@ -7,7 +7,10 @@ tests/test_gpu_bn.py, and their check() cases here stay as the end-to-end anchor
 tests/strict_loss.py in tests/test_gpu_loss.py, the loss tests here stay (the reference's own fp32 goldens, and the 640 x 640
 shape, whose dpreds now also goes through strict_loss with its former limit as the guard); the pool, upsample, copy, add_n,
 transpose, bucket and weight-pack leaves are held to tests/strict_move.py in tests/test_gpu_move.py (the pool's argmax compared
-exactly, slices with their neighbours), their cases here stay as the anchor.  check():
+exactly, slices with their neighbours), their cases here stay as the anchor; head decode, DFL, NMS and the validation
+kernels (csrc/decode_nms.hip) are held to tests/strict_post.py in tests/test_gpu_post.py (decode inside a derived bound, NMS
+rows and validation counters bit for bit against the oracle at every structural edge), the decode and NMS tests here stay
+(the reference's goldens and the config-5 tensor).  check():
 tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
 and round once, the stand-in does the same from the same rounded inputs, so 2 output ulps
 (bf16: 2^-7, f16: 2^-10 relative) of the tensor's max magnitude.  Integer outputs (pool argmax,

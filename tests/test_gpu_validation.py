@@ -38,6 +38,10 @@ def test_decode_predictions_matches_reference_golden():
 @pytest.mark.parametrize("dtype,conf,top_k", [(torch.float32, 0.25, 100), (torch.bfloat16, 0.25, 100),
                                                (torch.float16, 0.5, 7), (torch.float32, 0.999, 100)])
 def test_val_select_vs_oracle(dtype, conf, top_k):
+    """the anchor against the CPU's own arithmetic: counts, classes and boxes equal to torch's sigmoid / max on the CPU,
+    on inputs (seed 5) that put no anchor on a boundary where the two sigmoids could differ.  What separates "wrong" from
+    "undecidable" on any input, the structural edges and the NaN cases are held by tests/strict_post.py (post_select) in
+    tests/test_gpu_post.py"""
     from src.hipops import ops
     g = torch.Generator().manual_seed(5)
     n, nc, m = 3, 80, 2100
