@@ -16,6 +16,8 @@
 // image has in slot k; the last launch converts, normalises and writes NCHW in the model's input dtype.
 // Mosaic (no reference counterpart; opt-in): k_mosaic takes the place of the resize launch and composes each output from
 // four resized tiles of the batch's own images around a centre, fill elsewhere; the colour chain behind it is the same.
+// Affine warp (no reference counterpart; opt-in): k_affine gathers the finished canvas of the resize or mosaic launch through
+// an inverse 2x3 matrix, bilinear with a constant `fill` border, into a second staging buffer; the colour chain runs on that.
 #include "common.h"
 
 struct PrepImage {
@@ -36,6 +38,10 @@ struct MosaicTile {
     int x0, y0;         // canvas position of the tile's pixel (0, 0); may be negative (the quadrant clips the tile)
     int cx, cy;         // the output's centre, repeated in its four tiles
 };
+
+// the inverse map of one output's warp, canvas <- output, in continuous coordinates (pixel i covers [i, i + 1)): the six fp32
+// values the host rounded once from the float64 inverse of the forward matrix
+struct AffineRec { float a00, a01, b0, a10, a11, b1; };
 
 namespace {
 
@@ -113,6 +119,49 @@ __global__ __launch_bounds__(256) void k_mosaic(const unsigned char* __restrict_
     if (lx >= 0 && lx < t.tw && ly >= 0 && ly < t.th) resize_pixel(src + t.off, t.H, t.W, t.flip, ly, lx, t.th, t.tw, px);
 #pragma unroll
     for (int c = 0; c < 3; ++c) stage[(((long)n * 3 + c) * S + oy) * S + ox] = px[c];
+}
+
+// affine warp: one thread per output pixel, all three channels; 32 x 8 pixels per workgroup, so that a rotated workgroup
+// reads a compact patch of the canvas.  Operation order (every operation rounds once; no contraction in this file):
+//   px = ox + 0.5f, py = oy + 0.5f;  u = ((a00 * px + a01 * py) + b0) - 0.5f;  v = ((a10 * px + a11 * py) + b1) - 0.5f
+//   u or v outside [-1, S) (tested in float; a NaN fails it too): all four taps lie outside, the pixel is `fill`, nothing is
+//   read and no float is converted to int
+//   x0 = floor(u), fx = u - x0 (y likewise), so x0 in [-1, S - 1]; a tap with an index outside [0, S) is `fill`, every load
+//   is therefore inside the canvas
+//   top = p00 + fx * (p01 - p00), bot = p10 + fx * (p11 - p10), acc = top + fy * (bot - top): fx = fy = 0 gives p00 itself
+//   level = clamp(floor(acc + 0.5f), 0, 255), as resize_pixel quantises
+__global__ __launch_bounds__(256) void k_affine(const unsigned char* __restrict__ stage, const AffineRec* __restrict__ recs,
+                                               unsigned char* __restrict__ stage2, int S, int fill) {
+    const int n = blockIdx.z;
+    const int ox = blockIdx.x * 32 + (threadIdx.x & 31), oy = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (ox >= S || oy >= S) return;
+    const AffineRec A = recs[n];
+    const float px = (float)ox + 0.5f, py = (float)oy + 0.5f;
+    const float u = ((A.a00 * px + A.a01 * py) + A.b0) - 0.5f;
+    const float v = ((A.a10 * px + A.a11 * py) + A.b1) - 0.5f;
+    const float ff = (float)fill, fs = (float)S;
+    const long hw = (long)S * S;
+    float acc[3] = {ff, ff, ff};
+    if (u >= -1.f && u < fs && v >= -1.f && v < fs) {
+        const float xf = floorf(u), yf = floorf(v);
+        const float fx = u - xf, fy = v - yf;
+        const int x0 = (int)xf, y0 = (int)yf;                 // in [-1, S - 1] by the test above
+        const bool l = x0 >= 0, r = x0 + 1 < S, t = y0 >= 0, b = y0 + 1 < S;
+        const unsigned char* base = stage + (long)n * 3 * hw;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const unsigned char* pl = base + c * hw;
+            const float p00 = (t && l) ? (float)pl[(long)y0 * S + x0] : ff;
+            const float p01 = (t && r) ? (float)pl[(long)y0 * S + x0 + 1] : ff;
+            const float p10 = (b && l) ? (float)pl[(long)(y0 + 1) * S + x0] : ff;
+            const float p11 = (b && r) ? (float)pl[(long)(y0 + 1) * S + x0 + 1] : ff;
+            const float top = p00 + fx * (p01 - p00), bot = p10 + fx * (p11 - p10);
+            acc[c] = top + fy * (bot - top);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        stage2[(long)n * 3 * hw + c * hw + (long)oy * S + ox] = (unsigned char)fminf(fmaxf(floorf(acc[c] + 0.5f), 0.f), 255.f);
 }
 
 __device__ __forceinline__ float gray_of(float r, float g, float b) { return floorf(0.2989f * r + 0.587f * g + 0.114f * b); }
@@ -226,6 +275,19 @@ int yolo_mosaic_tile_fill(void* table_host, int image, int tile, long off, int H
     return YOLO_OK;
 }
 
+int yolo_affine_bytes(void) { return (int)sizeof(AffineRec); }
+
+// fill record `index` of the host-side affine table: the inverse map (canvas <- output), finite values only
+int yolo_affine_fill(void* table_host, int index, float a00, float a01, float b0, float a10, float a11, float b1) {
+    const float v[6] = {a00, a01, b0, a10, a11, b1};
+    for (int k = 0; k < 6; ++k)
+        if (!(v[k] - v[k] == 0.f)) return YOLO_ERR_ARG;       // inf - inf and nan - nan are nan
+    if (index < 0) return YOLO_ERR_ARG;
+    AffineRec& a = ((AffineRec*)table_host)[index];
+    a.a00 = a00; a.a01 = a01; a.b0 = b0; a.a10 = a10; a.a11 = a11; a.b1 = b1;
+    return YOLO_OK;
+}
+
 }  // extern "C"
 
 // the colour chain on the staging buffer: per jitter slot a gray-mean reduction and that slot's op, the last launch
@@ -277,6 +339,27 @@ int yolo_image_prep_mosaic(const void* src, const void* tiles_dev, const void* t
     hipLaunchKernelGGL(k_mosaic, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src,
                        (const MosaicTile*)tiles_dev, (unsigned char*)stage, S, fill);
     return color_chain((const PrepImage*)table_dev, N, S, jitter, stage, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+}
+
+// the same with an affine warp between the canvas and the colour chain: tiles_dev = nullptr -> k_resize_flip writes the canvas,
+// else k_mosaic; k_affine gathers it through affine_dev ([N] yolo_affine_fill records) into stage2 ([N][3][S][S] uint8, not
+// overlapping stage), and the colour chain runs on stage2.  `fill` is the level of the mosaic's empty quadrants and of the
+// warp's uncovered pixels
+int yolo_image_prep_affine(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, int N, int S,
+                           int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype, float m0,
+                           float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
+    if (N <= 0 || S <= 0 || fill < 0 || fill > 255 || affine_dev == nullptr || stage2 == nullptr || stage2 == stage)
+        return YOLO_ERR_ARG;
+    const PrepImage* imgs = (const PrepImage*)table_dev;
+    if (tiles_dev == nullptr)
+        hipLaunchKernelGGL(k_resize_flip, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src, imgs,
+                           (unsigned char*)stage, S);
+    else
+        hipLaunchKernelGGL(k_mosaic, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src,
+                           (const MosaicTile*)tiles_dev, (unsigned char*)stage, S, fill);
+    hipLaunchKernelGGL(k_affine, dim3(ceil_div(S, 32), ceil_div(S, 8), N), dim3(256), 0, st, (const unsigned char*)stage,
+                       (const AffineRec*)affine_dev, (unsigned char*)stage2, S, fill);
+    return color_chain(imgs, N, S, jitter, stage2, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
 }
 
 }  // extern "C"

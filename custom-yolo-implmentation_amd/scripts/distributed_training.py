@@ -121,7 +121,11 @@ def main(args):
             device=args.device, num_classes=model_cfg["num_classes"],
             # optional key `data.mosaic: {p, gain, fill, min_box, min_visible, max_boxes, close_epochs}`: four-image mosaics
             # composed from each batch's own images inside the on-device transform (absent = off; the reference has none)
-            mosaic=data_cfg.get("mosaic"))
+            mosaic=data_cfg.get("mosaic"),
+            # optional key `data.affine: {degrees, translate, scale, shear, fill, min_box, min_visible, max_aspect, max_boxes,
+            # close_epochs}`: a random rotation / scale / shear / translation of the finished canvas (plain or mosaic) with the
+            # boxes following, one more launch in the on-device transform (absent = off; the reference has none)
+            affine=data_cfg.get("affine"))
         # optional key `training.max_grad_norm`: global-norm gradient clipping inside the optimizer step (absent = off).
         # The reference's `training.grad_clip` is dead there (its loop never reads it) and stays ignored here, so a
         # reference config keeps reference numerics.

@@ -11,7 +11,9 @@ decisions are drawn on the host in torchvision's order (flip: one `torch.rand(1)
 uniform per factor), boxes follow the geometry (XYWH: x' = W - x - w for a flip, then scaling by 640/W, 640/H) and the
 batch leaves in the format of src/data/collate.py: (images[N,3,S,S], [target dicts with "boxes" (Mi, 5)]).
 With `mosaic=` set (opt-in, no reference counterpart), an output is composed of four resized images of its own batch around
-a random centre, in the same launch sequence (`k_mosaic` in the resize launch's place), with its boxes clipped on the host."""
+a random centre, in the same launch sequence (`k_mosaic` in the resize launch's place), with its boxes clipped on the host.
+With `affine=` set (opt-in, no reference counterpart), the finished canvas -- plain resize or mosaic -- is warped by a random
+rotation, scale, shear and translation in one more launch (`k_affine`) before the colour chain, and the boxes follow."""
 import math
 
 import numpy as np
@@ -22,6 +24,8 @@ from src.hipops import ops
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
 MOSAIC_DEFAULTS = dict(p=1.0, gain=(0.4, 1.0), fill=114, min_box=2.0, min_visible=0.1, max_boxes=128, close_epochs=0)
+AFFINE_DEFAULTS = dict(degrees=0.0, translate=0.1, scale=0.5, shear=0.0, fill=114, min_box=2.0, min_visible=0.1, max_aspect=100.0,
+                       max_boxes=128, close_epochs=0)
 
 
 def _uniform(lo, hi):
@@ -80,13 +84,71 @@ def mosaic_boxes(record, targets, sizes, size, min_box, min_visible, max_boxes):
     return out
 
 
+def affine_matrix(draw, size):
+    """A `sample_affine` draw (angle, gain, shear x, shear y, tx, ty; degrees) -> the forward 2 x 3 matrix canvas -> output,
+    float64, M = T Sh R C in continuous pixel coordinates (pixel i covers [i, i + 1), its centre is i + 0.5): C moves the
+    canvas centre (size / 2, size / 2) to the origin, R rotates by the angle and scales by the gain, Sh has tan(shear x) at
+    [0, 1] and tan(shear y) at [1, 0], T translates by (tx size, ty size)."""
+    angle, gain, shx, shy, tx, ty = (float(v) for v in draw)
+    c = np.array([[1.0, 0.0, -size / 2], [0.0, 1.0, -size / 2], [0.0, 0.0, 1.0]])
+    a = math.radians(angle)
+    r = np.array([[gain * math.cos(a), -gain * math.sin(a), 0.0], [gain * math.sin(a), gain * math.cos(a), 0.0], [0.0, 0.0, 1.0]])
+    sh = np.array([[1.0, math.tan(math.radians(shx)), 0.0], [math.tan(math.radians(shy)), 1.0, 0.0], [0.0, 0.0, 1.0]])
+    t = np.array([[1.0, 0.0, tx * size], [0.0, 1.0, ty * size], [0.0, 0.0, 1.0]])
+    return (t @ sh @ r @ c)[:2]
+
+
+def affine_record(m):
+    """Forward 2 x 3 matrix -> the record k_affine takes: the six values (a00, a01, b0, a10, a11, b1) of the INVERSE map,
+    formed in float64 and rounded once to fp32.  A non-finite or singular matrix is refused."""
+    m = np.asarray(m, np.float64)
+    if m.shape != (2, 3) or not np.isfinite(m).all():
+        raise ValueError(f"affine: a forward matrix is 2 x 3 and finite, got {m.tolist()}")
+    det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    if not abs(det) > 1e-12 * max(1.0, float(np.abs(m[:, :2]).max()) ** 2):
+        raise ValueError(f"affine: singular matrix (determinant {det})")
+    a = np.array([[m[1, 1], -m[0, 1]], [-m[1, 0], m[0, 0]]]) / det
+    b = -a @ m[:, 2]
+    rec = np.array([a[0, 0], a[0, 1], b[0], a[1, 0], a[1, 1], b[1]]).astype(np.float32)
+    if not np.isfinite(rec).all():
+        raise ValueError(f"affine: the inverse of {m.tolist()} is not finite in fp32")
+    return tuple(float(v) for v in rec)
+
+
+def affine_boxes(m, boxes5, size, min_box, min_visible, max_aspect, max_boxes):
+    """Boxes (M, 5) float32 (x, y, w, h, label) on the canvas -> on the warped output: the four corners through the forward
+    matrix `m`, their axis-aligned hull clipped to [0, size]; a box stays when both clipped sides are >= min_box, when
+    w'h' / (w h gain^2 + 1e-9) >= min_visible (gain^2 = |det| of the matrix: the area scale) and when its aspect ratio
+    max(w'/h', h'/w') < max_aspect.  Order kept; beyond max_boxes the largest clipped areas stay, in that order."""
+    b = boxes5.float().reshape(-1, 5)
+    mt = torch.as_tensor(np.asarray(m, np.float64), dtype=torch.float32)
+    if b.shape[0] == 0:
+        return torch.zeros(0, 5)
+    x1, y1, x2, y2 = b[:, 0], b[:, 1], b[:, 0] + b[:, 2], b[:, 1] + b[:, 3]
+    cx = torch.stack([x1, x2, x1, x2], 1)
+    cy = torch.stack([y1, y1, y2, y2], 1)
+    wx = mt[0, 0] * cx + mt[0, 1] * cy + mt[0, 2]
+    wy = mt[1, 0] * cx + mt[1, 1] * cy + mt[1, 2]
+    nx1, nx2 = wx.min(1).values.clamp(0, size), wx.max(1).values.clamp(0, size)
+    ny1, ny2 = wy.min(1).values.clamp(0, size), wy.max(1).values.clamp(0, size)
+    cw, ch = nx2 - nx1, ny2 - ny1
+    gain2 = (mt[0, 0] * mt[1, 1] - mt[0, 1] * mt[1, 0]).abs()
+    aspect = torch.maximum(cw / ch, ch / cw)
+    keep = (cw >= min_box) & (ch >= min_box) & (cw * ch / (b[:, 2] * b[:, 3] * gain2 + 1e-9) >= min_visible) & (aspect < max_aspect)
+    out, area = torch.stack([nx1, ny1, cw, ch, b[:, 4]], 1)[keep], (cw * ch)[keep]
+    if out.shape[0] > max_boxes:
+        top = torch.sort(area, descending=True, stable=True).indices[:max_boxes]
+        out = out[torch.sort(top).values]
+    return out
+
+
 class BatchTransform:
     """Callable(images, targets) -> (batch on `device`, targets).  images: decoded RGB images as uint8 (H, W, 3) arrays /
     tensors or PIL images; targets: dicts with "boxes" (M, 4) XYWH pixels and "labels" (M, 1) (the reference dataset's
     items before its transform) or None."""
 
     def __init__(self, train, size=640, device="cuda", dtype=torch.float32, flip_p=0.5, brightness=0.2, contrast=0.2,
-                 saturation=0.2, hue=0.1, mean=MEAN, std=STD, mosaic=None):
+                 saturation=0.2, hue=0.1, mean=MEAN, std=STD, mosaic=None, affine=None):
         self.train, self.size, self.device, self.dtype = train, size, torch.device(device), dtype
         self.flip_p, self.jit = flip_p, (brightness, contrast, saturation, hue)
         self.mean, self.std = mean, std
@@ -111,6 +173,30 @@ class BatchTransform:
                                min_visible=float(m["min_visible"]), max_boxes=int(m["max_boxes"]),
                                close_epochs=int(m["close_epochs"]))
         self.mosaic_on = self.mosaic is not None
+        # affine: None (off: today's path, call for call) or a dict of AFFINE_DEFAULTS' keys; `affine_on` is its per-epoch switch
+        self.affine = None
+        if affine is not None:
+            if not train:
+                raise ValueError("affine is a training augmentation: the validation transform takes none")
+            unknown = set(affine) - set(AFFINE_DEFAULTS)
+            if unknown:
+                raise ValueError(f"affine: unknown keys {sorted(unknown)}; expected {sorted(AFFINE_DEFAULTS)}")
+            a = {**AFFINE_DEFAULTS, **affine}
+            if not 0.0 <= a["degrees"] <= 180.0 or not 0.0 <= a["shear"] <= 89.0:
+                raise ValueError(f"affine.degrees must lie in [0, 180] and affine.shear in [0, 89], got {a['degrees']}, {a['shear']}")
+            if not 0.0 <= a["translate"] < 1.0 or not 0.0 <= a["scale"] < 1.0:
+                raise ValueError(f"affine.translate and affine.scale must lie in [0, 1), got {a['translate']}, {a['scale']}")
+            if int(a["fill"]) != a["fill"] or not 0 <= int(a["fill"]) <= 255 or int(a["max_boxes"]) < 1 or int(a["close_epochs"]) < 0:
+                raise ValueError("affine: fill is a uint8 level, max_boxes >= 1 and close_epochs >= 0")
+            if a["min_box"] < 0 or a["min_visible"] < 0 or not a["max_aspect"] > 1:
+                raise ValueError("affine: min_box >= 0, min_visible >= 0 and max_aspect > 1")
+            if self.mosaic is not None and self.mosaic["fill"] != int(a["fill"]):
+                raise ValueError(f"affine.fill ({a['fill']}) and mosaic.fill ({self.mosaic['fill']}) are one level: the launch takes one")
+            self.affine = dict(degrees=float(a["degrees"]), translate=float(a["translate"]), scale=float(a["scale"]),
+                               shear=float(a["shear"]), fill=int(a["fill"]), min_box=float(a["min_box"]),
+                               min_visible=float(a["min_visible"]), max_aspect=float(a["max_aspect"]),
+                               max_boxes=int(a["max_boxes"]), close_epochs=int(a["close_epochs"]))
+        self.affine_on = self.affine is not None
         self._pinned = None                 # reused pinned upload buffer (one memcpy per image into it, one async H2D per batch)
         self._uploaded = None
 
@@ -144,6 +230,32 @@ class BatchTransform:
             out.append((cx, cy, partners, gains, flips))
         return out
 
+    def sample_affine(self, n):
+        """The warp decisions of a batch of `n` images, drawn after its `n` sample() calls and after sample_mosaic(n) when the
+        mosaic is on (both sequences unchanged): per output six uniform draws, also when a range is 0 -- angle, gain, shear x,
+        shear y (degrees), tx, ty (fractions of the size; 0.5 keeps the centre)."""
+        if self.affine is None:
+            raise ValueError("sample_affine: this transform was built without affine=")
+        a = self.affine
+        return [(_uniform(-a["degrees"], a["degrees"]), _uniform(1 - a["scale"], 1 + a["scale"]), _uniform(-a["shear"], a["shear"]),
+                 _uniform(-a["shear"], a["shear"]), _uniform(0.5 - a["translate"], 0.5 + a["translate"]),
+                 _uniform(0.5 - a["translate"], 0.5 + a["translate"])) for _ in range(n)]
+
+    def _affine_matrices(self, affine, n):
+        """Per output the forward 2 x 3 matrix (float64), from draws (six values), ready matrices or None (identity)."""
+        if len(affine) != n:
+            raise ValueError(f"affine: {len(affine)} records for {n} images")
+        out = []
+        for a in affine:
+            if a is None:
+                out.append(np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]))
+                continue
+            a = np.asarray(a, np.float64)
+            if a.shape not in ((6,), (2, 3)):
+                raise ValueError(f"affine: a record is a draw of six values or a 2 x 3 forward matrix, got shape {a.shape}")
+            out.append(affine_matrix(a, self.size) if a.shape == (6,) else a)
+        return out
+
     @staticmethod
     def _as_u8(img):
         if isinstance(img, torch.Tensor):
@@ -154,9 +266,10 @@ class BatchTransform:
             raise ValueError("BatchTransform takes decoded RGB images as uint8 (H, W, 3)")
         return t.contiguous()
 
-    def __call__(self, images, targets=None, params=None, mosaic=None):
+    def __call__(self, images, targets=None, params=None, mosaic=None, affine=None):
         """`params`: the per-image sample() decisions; `mosaic`: per output None (plain), a sample_mosaic() draw or a
-        geometry record (`mosaic_geometry`'s format) -- both are drawn here when not given."""
+        geometry record (`mosaic_geometry`'s format); `affine`: per output None (identity), a sample_affine() draw or a
+        forward 2 x 3 matrix -- all are drawn here when not given."""
         imgs = [self._as_u8(i) for i in images]
         params = params if params is not None else [self.sample() for _ in imgs]
         if mosaic is not None and self.mosaic is None:
@@ -164,6 +277,12 @@ class BatchTransform:
         use_mosaic = self.mosaic is not None and (self.mosaic_on or mosaic is not None)
         if use_mosaic and mosaic is None:
             mosaic = self.sample_mosaic(len(imgs))
+        if affine is not None and self.affine is None:
+            raise ValueError("affine records were passed to a BatchTransform built without affine=")
+        use_affine = self.affine is not None and (self.affine_on or affine is not None)
+        if use_affine:
+            mats = self._affine_matrices(affine if affine is not None else self.sample_affine(len(imgs)), len(imgs))
+            inverse = [affine_record(m) for m in mats]
         recs, off = [], 0
         for t, (flip, order, fac) in zip(imgs, params):
             h, w = int(t.shape[0]), int(t.shape[1])
@@ -182,31 +301,36 @@ class BatchTransform:
         else:
             flat = torch.cat([t.reshape(-1) for t in imgs])
         jitter = self.train and any(len(p[1]) for p in params)
-        if use_mosaic:
-            records = self._mosaic_records(mosaic, recs)
+        records = self._mosaic_records(mosaic, recs) if use_mosaic else [None] * len(recs)
+        if use_affine:
+            tiles = self._mosaic_tiles(records, recs) if use_mosaic else None
+            batch = ops.image_prep_affine(flat, recs, tiles, inverse, self.size, self.affine["fill"], jitter, self.dtype, self.mean,
+                                          self.std)
+        elif use_mosaic:
             batch = ops.image_prep_mosaic(flat, recs, self._mosaic_tiles(records, recs), self.size, self.mosaic["fill"], jitter,
                                           self.dtype, self.mean, self.std)
         else:
-            records = [None] * len(recs)
             batch = ops.image_prep(flat, recs, self.size, jitter, self.dtype, self.mean, self.std)
         out_t = None
         if targets is not None:
             out_t = []
             sizes = [(r[1], r[2]) for r in recs]
-            for tg, (_, h, w, flip, _, _), rec in zip(targets, recs, records):
+            for i, (tg, (_, h, w, flip, _, _), rec) in enumerate(zip(targets, recs, records)):
+                new = {k: v for k, v in tg.items() if k not in ("boxes", "labels")}
                 if rec is not None:
                     m = self.mosaic
-                    new = {k: v for k, v in tg.items() if k not in ("boxes", "labels")}
                     new["boxes"] = mosaic_boxes(rec, targets, sizes, self.size, m["min_box"], m["min_visible"], m["max_boxes"])
-                    out_t.append(new)
-                    continue
-                b = tg["boxes"].clone().float().reshape(-1, 4)
-                if flip:
-                    b[:, 0] = w - (b[:, 0] + b[:, 2])
-                b[:, [0, 2]] *= self.size / w
-                b[:, [1, 3]] *= self.size / h
-                new = {k: v for k, v in tg.items() if k not in ("boxes", "labels")}
-                new["boxes"] = torch.cat([b, tg["labels"].float().reshape(-1, 1)], 1)      # dataset_loader.py:76
+                else:
+                    b = tg["boxes"].clone().float().reshape(-1, 4)
+                    if flip:
+                        b[:, 0] = w - (b[:, 0] + b[:, 2])
+                    b[:, [0, 2]] *= self.size / w
+                    b[:, [1, 3]] *= self.size / h
+                    new["boxes"] = torch.cat([b, tg["labels"].float().reshape(-1, 1)], 1)      # dataset_loader.py:76
+                if use_affine:
+                    a = self.affine
+                    new["boxes"] = affine_boxes(mats[i], new["boxes"], self.size, a["min_box"], a["min_visible"], a["max_aspect"],
+                                                a["max_boxes"])
                 out_t.append(new)
         return batch, out_t
 
@@ -239,8 +363,8 @@ class BatchTransform:
         return out
 
 
-def get_train_transforms(size=640, device="cuda", dtype=torch.float32, mosaic=None):
-    return BatchTransform(True, size, device, dtype, mosaic=mosaic)
+def get_train_transforms(size=640, device="cuda", dtype=torch.float32, mosaic=None, affine=None):
+    return BatchTransform(True, size, device, dtype, mosaic=mosaic, affine=affine)
 
 
 def get_val_transforms(size=640, device="cuda", dtype=torch.float32):

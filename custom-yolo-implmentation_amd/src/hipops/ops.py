@@ -752,6 +752,21 @@ def image_prep(src_u8, recs, size, jitter, dtype, mean, std):
     return out
 
 
+def _tile_table_fill(host_ptr, tiles, limit, who):
+    """The MosaicTile records of `tiles` into the (pinned, zeroed) host table at `host_ptr`."""
+    for i, (cx, cy, quad) in enumerate(tiles):
+        if len(quad) != 4 or quad[0] is None:
+            raise ValueError(f"{who}: an output has four tile slots and tile 0 is always present")
+        for k, t in enumerate(quad):
+            if t is None:
+                continue
+            off, h, w, flip, tw, th, x0, y0 = t
+            if off < 0 or off + h * w * 3 > limit:
+                raise ValueError(f"{who}: tile {k} of output {i} reads outside the source buffer")
+            lib.call("yolo_mosaic_tile_fill", host_ptr, i, k, int(off), int(h), int(w), int(bool(flip)), int(tw),
+                     int(th), int(x0), int(y0), int(cx), int(cy))
+
+
 def image_prep_mosaic(src_u8, recs, tiles, size, fill, jitter, dtype, mean, std):
     """`image_prep` with a mosaic in front of the colour chain.  recs: as for `image_prep`, one per OUTPUT image (its jitter
     order and factors are what is read); tiles: per output (cx, cy, [four of (offset, H, W, flip, tw, th, x0, y0) or None]):
@@ -764,17 +779,7 @@ def image_prep_mosaic(src_u8, recs, tiles, size, fill, jitter, dtype, mean, std)
     rb, tb = lib.query("yolo_prep_image_bytes"), lib.query("yolo_mosaic_tile_bytes")
     host = torch.zeros(n * rb + 4 * n * tb, dtype=torch.uint8).pin_memory()
     _prep_table_fill(host, recs)
-    for i, (cx, cy, quad) in enumerate(tiles):
-        if len(quad) != 4 or quad[0] is None:
-            raise ValueError("image_prep_mosaic: an output has four tile slots and tile 0 is always present")
-        for k, t in enumerate(quad):
-            if t is None:
-                continue
-            off, h, w, flip, tw, th, x0, y0 = t
-            if off < 0 or off + h * w * 3 > src_u8.numel():
-                raise ValueError(f"image_prep_mosaic: tile {k} of output {i} reads outside the source buffer")
-            lib.call("yolo_mosaic_tile_fill", host.data_ptr() + n * rb, i, k, int(off), int(h), int(w), int(bool(flip)), int(tw),
-                     int(th), int(x0), int(y0), int(cx), int(cy))
+    _tile_table_fill(host.data_ptr() + n * rb, tiles, src_u8.numel(), "image_prep_mosaic")
     table = host.to(src_u8.device, non_blocking=True)
     stage = torch.empty((n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
     means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
@@ -782,6 +787,35 @@ def image_prep_mosaic(src_u8, recs, tiles, size, fill, jitter, dtype, mean, std)
     lib.call("yolo_image_prep_mosaic", _p(src_u8), _p(table) + n * rb, _p(table), n, size,
              int(fill), int(bool(jitter)), _p(stage), _p(means), _p(out), dt(dtype), *[float(v) for v in mean],
              *[float(v) for v in std], st)
+    return out
+
+
+def image_prep_affine(src_u8, recs, tiles, affine, size, fill, jitter, dtype, mean, std):
+    """`image_prep` (tiles None) or `image_prep_mosaic` (tiles as there) with an affine warp between the finished canvas and
+    the colour chain.  affine: per output the six fp32 values (a00, a01, b0, a10, a11, b1) of the INVERSE map, canvas <-
+    output, in continuous pixel coordinates; uncovered pixels are `fill`.  The PrepImage table, the tile table and the affine
+    table travel in one pinned buffer and one upload."""
+    st = _stream(src_u8)
+    n = len(recs)
+    if len(affine) != n or (tiles is not None and len(tiles) != n):
+        raise ValueError(f"image_prep_affine: {n} records need {n} affine records and, if any, {n} tile sets")
+    rb, tb, ab = lib.query("yolo_prep_image_bytes"), lib.query("yolo_mosaic_tile_bytes"), lib.query("yolo_affine_bytes")
+    nt = 4 * n * tb if tiles is not None else 0
+    host = torch.zeros(n * rb + nt + n * ab, dtype=torch.uint8).pin_memory()
+    _prep_table_fill(host, recs)
+    if tiles is not None:
+        _tile_table_fill(host.data_ptr() + n * rb, tiles, src_u8.numel(), "image_prep_affine")
+    for i, a in enumerate(affine):
+        if len(a) != 6:
+            raise ValueError(f"image_prep_affine: record {i} needs six values, got {len(a)}")
+        lib.call("yolo_affine_fill", host.data_ptr() + n * rb + nt, i, *[float(v) for v in a])
+    table = host.to(src_u8.device, non_blocking=True)
+    stage = torch.empty((2, n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
+    means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
+    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
+    lib.call("yolo_image_prep_affine", _p(src_u8), _p(table) + n * rb if tiles is not None else 0, _p(table),
+             _p(table) + n * rb + nt, n, size, int(fill), int(bool(jitter)), _p(stage[0]), _p(stage[1]), _p(means), _p(out),
+             dt(dtype), *[float(v) for v in mean], *[float(v) for v in std], st)
     return out
 
 

@@ -260,6 +260,15 @@ int yolo_image_prep(const void* src, const void* table_dev, int N, int S, int ji
 int yolo_mosaic_tile_bytes();
 int yolo_mosaic_tile_fill(void* table_host, int image, int tile, long off, int H, int W, int flip, int tw, int th, int x0, int y0, int cx, int cy);
 int yolo_image_prep_mosaic(const void* src, const void* tiles_dev, const void* table_dev, int N, int S, int fill, int jitter, void* stage, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
+/* random affine warp between the canvas and the same colour chain (no reference counterpart: src/data/transforms.py:4-14 has flip, resize and
+   ColorJitter only): output pixel (ox, oy) of image i samples the finished canvas (tiles_dev == nullptr: the plain resize, else the mosaic) at
+   u = a00 (ox + 0.5) + a01 (oy + 0.5) + b0 - 0.5, v likewise -- continuous coordinates, pixel i covers [i, i + 1) -- bilinear in fp32 with a
+   constant `fill` border, rounded like the resize.  affine_dev: [N] records (yolo_affine_fill) holding the INVERSE map, canvas <- output, as
+   six fp32 values; stage2: a second uint8 [N][3][S][S] scratch the warp writes and the colour chain reads.  `fill` also serves k_mosaic.
+   The record (1, 0, 0, 0, 1, 0) reproduces yolo_image_prep / yolo_image_prep_mosaic bit for bit */
+int yolo_affine_bytes();
+int yolo_affine_fill(void* table_host, int index, float a00, float a01, float b0, float a10, float a11, float b1);
+int yolo_image_prep_affine(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, int N, int S, int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
 
 /* ---- hardware self-tests (instruction semantics the tiled kernels assume; tests/test_gpu_selftest.py; no reference counterpart: model_blocks.py:1) */
 int yolo_selftest_tr16(const void* tile_in, void* out, hipStream_t st);

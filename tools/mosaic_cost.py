@@ -4,12 +4,14 @@
 mosaic, plain, ...), so drift of the box hits both alike.  The mosaic decisions are drawn once and reused, like the plain
 ones, so the windows time the upload and the launches, not the host RNG.
 
-    python tools/mosaic_cost.py [--batches 10] [--rounds 7] [--gain 0.4 1.0] [--plain-only]
+    python tools/mosaic_cost.py [--batches 10] [--rounds 7] [--gain 0.4 1.0] [--plain-only] [--affine]
 
 `--gain 1 1` keeps every tile at the plain resize's scale (same taps per pixel as the plain path, fewer pixels sampled):
 with it the difference to the default gain separates the larger antialias footprints of shrunken tiles from the cost of
 the quadrant test and the divergence at the quadrant edges.  `--plain-only` times the plain path alone (a checkout without
-the mosaic).  Prints one JSON line.  (Kernel rows: run under `rocprofv3 --kernel-trace --stats -d DIR -- python
+the mosaic).  `--affine` adds the warp's two batches to the alternation: `affine={"degrees": 10, "shear": 2}` behind the plain
+resize and behind the mosaic, decisions drawn once (kernel rows: k_affine beside k_resize_flip / k_mosaic; it reads and writes
+N * 3 * S * S bytes).  Prints one JSON line.  (Kernel rows: run under `rocprofv3 --kernel-trace --stats -d DIR -- python
 tools/mosaic_cost.py --rounds 2` and compare k_resize_flip with k_mosaic.)"""
 import argparse
 import json
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--gain", type=float, nargs=2, default=[0.4, 1.0])
     ap.add_argument("--plain-only", action="store_true")
+    ap.add_argument("--affine", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mosaic_cost.py needs an MI355X")
@@ -65,6 +68,14 @@ def main():
         mos = BatchTransform(True, size=640, device="cuda", dtype=torch.bfloat16, mosaic={"p": 1.0, "gain": args.gain})
         draws = mos.sample_mosaic(len(imgs))
         calls["mosaic"] = lambda: mos(imgs, params=params, mosaic=draws)
+    if args.affine:
+        acfg = {"degrees": 10.0, "shear": 2.0}
+        aff = BatchTransform(True, size=640, device="cuda", dtype=torch.bfloat16, affine=acfg)
+        warps = aff.sample_affine(len(imgs))
+        calls["affine"] = lambda: aff(imgs, params=params, affine=warps)
+        if not args.plain_only:
+            both = BatchTransform(True, size=640, device="cuda", dtype=torch.bfloat16, mosaic={"p": 1.0, "gain": args.gain}, affine=acfg)
+            calls["mosaic_affine"] = lambda: both(imgs, params=params, mosaic=draws, affine=warps)
     for call in calls.values():
         for _ in range(args.warmup):
             call()
@@ -83,6 +94,9 @@ def main():
     if "mosaic" in times:
         out["gain"] = args.gain
         out["mosaic_over_plain"] = round(out["median_mosaic_ms"] / out["median_plain_ms"], 3)
+    for k in ("affine", "mosaic_affine"):
+        if k in times:
+            out[f"{k}_over_plain"] = round(out[f"median_{k}_ms"] / out["median_plain_ms"], 3)
     print(json.dumps(out), flush=True)
 
 
