@@ -2,6 +2,7 @@
 reference spells as several ATen ops; the forward saves exactly what its hand-written backward needs.
 All leaf calls go through the `ops` module namespace (tests swap leaves for a torch emulation to check
 this wiring on a machine without a GPU; the product never does)."""
+import contextlib
 import os
 
 import torch
@@ -44,28 +45,78 @@ def deterministic_stats():
     return DETERMINISTIC or torch.are_deterministic_algorithms_enabled()
 
 
-_SIDE = {}
 OVERLAP_WGRAD = True        # run a conv's weight gradient on a side stream, concurrently with its data gradient
-FWD_STREAM = None           # see ConvBnAct.forward
+FWD_STREAM = None           # see _on_fwd_stream
 HEAD_TWO_STREAMS = os.environ.get("YOLO_HEAD_STREAMS", "1") == "1"       # Head.forward; 0 for A/B runs
-LAZY_WGRAD_JOIN = False     # set by a caller that owns the whole backward (TrainStepRunner) and joins at its end
+LAZY_WGRAD_JOIN = False     # set by a caller that owns the whole backward and joins at its end: see lazy_param_grads
 # convs per cross-stream sync point in lazy mode.  Measured on preset s (img/s): per-layer fork/join 2238, 1: 2275,
 # 2: 2320, 4: 2339, 8: 2354-2368, 12: 2330, 16: 2322, 32: 2312, all at the end: 2217 (dy has left the caches by then);
 # grouping by queued bytes instead of by count was worse
 WGRAD_GROUP = int(os.environ.get("YOLO_WGRAD_GROUP", "8"))
-_INFLIGHT = {}              # device -> [(keepalive, fn)] of the work still running on the side stream
-_QUEUED = {}                # device -> [(keepalive, fn)] not yet issued
+JOIN_EACH_GROUP = os.environ.get("YOLO_WGRAD_JOIN", "1") == "1"
+
+
+class SideQueue:
+    """Deferred parameter-gradient work of one device: records (keepalive, fn) wait in `queued` until WGRAD_GROUP of them share
+    one sync point and are issued on the `side` stream; `inflight` keeps the inputs of what may still run there.  The streams are
+    handed in (`current()`: the stream the backward runs on, `entered(s)`: a context that makes s current): no device call here."""
+
+    def __init__(self, side, current, entered):
+        self.side, self.current, self.entered = side, current, entered
+        self.queued, self.inflight = [], []
+
+    def defer(self, keepalive, fn):
+        """In a LAZY_WGRAD_JOIN backward: queue `fn` (it must write into tensors allocated by the caller) and return True;
+        `keepalive` holds its inputs until the join after it ran.  Otherwise return False (the caller runs it inline)."""
+        if not (LAZY_WGRAD_JOIN and OVERLAP_WGRAD):
+            return False
+        self.queued.append((keepalive, fn))
+        if len(self.queued) >= WGRAD_GROUP:
+            self.sync(self.current())
+        return True
+
+    def sync(self, cur):
+        """One sync point: join what runs on the side stream, fork, issue every queued piece of work there.
+        The join releases the previous group's inputs (x, dy) and costs the main chain 35-125 us of idle time at most sync
+        points of a step (tools/queue_gaps.py: 0.6-0.9 ms per step: the side stream has not drained yet).  Dropping it
+        (YOLO_WGRAD_JOIN=0: inputs referenced until join(), one join at the end) was measured SLOWER in the replayed
+        graph, 12.32 vs 11.70 ms per step on the same box, at every group size: the side stream then lags without bound and
+        shares the chip with the main chain all the way through the large-map layers at the end of backward."""
+        jobs, self.queued = self.queued, []
+        if JOIN_EACH_GROUP:
+            if self.inflight:
+                cur.wait_stream(self.side)
+            self.inflight = jobs                # the previous group's inputs may be reused from here on
+        else:
+            self.inflight.extend(jobs)
+        if jobs:
+            self.side.wait_stream(cur)
+            with self.entered(self.side):
+                for _, fn in jobs:
+                    fn()
+
+    def join(self, cur):
+        """End of a LAZY_WGRAD_JOIN backward: issue what is still queued and wait for the side stream."""
+        self.sync(cur)
+        if self.inflight:
+            cur.wait_stream(self.side)
+        self.inflight = []
+
+
+_QUEUES, _STEP = {}, {}     # device -> SideQueue, device -> the step stream
+
+
+def _side_queue(dev):
+    """The device's SideQueue (made on first use on a HIP device), or None: nothing is ever deferred elsewhere."""
+    q = _QUEUES.get(dev)
+    if q is None and dev.type == "cuda":
+        q = _QUEUES[dev] = SideQueue(torch.cuda.Stream(dev), lambda: torch.cuda.current_stream(dev), torch.cuda.stream)
+    return q
 
 
 def side_stream(dev):
     """The one auxiliary HIP stream per device (graph capture of more forked streams is not reliable on this stack)."""
-    side = _SIDE.get(dev)
-    if side is None:
-        side = _SIDE[dev] = torch.cuda.Stream(dev)
-    return side
-
-
-_STEP = {}
+    return _side_queue(dev).side
 
 
 def step_stream(dev):
@@ -83,64 +134,58 @@ def step_stream(dev):
     return st
 
 
-JOIN_EACH_GROUP = os.environ.get("YOLO_WGRAD_JOIN", "1") == "1"
+def join_wgrad_stream(device):
+    """Issue what the device's SideQueue still holds and wait for the side stream (nothing to do where none exists)."""
+    device = torch.device(device)
+    if device.index is None and device.type == "cuda":
+        device = torch.device("cuda", torch.cuda.current_device())
+    q = _QUEUES.get(device)
+    if q is not None:
+        q.join(q.current())
 
 
-def _issue_wgrads(dev, cur, side):
-    """One sync point: join what runs on the side stream, fork, issue every queued piece of work there.
-    The join releases the previous group's inputs (x, dy) and costs the main chain 35-125 us of idle time at most sync
-    points of a step (tools/queue_gaps.py: 0.6-0.9 ms per step: the side stream has not drained yet).  Dropping it
-    (YOLO_WGRAD_JOIN=0: inputs referenced until join_wgrad_stream, one join at the end) was measured SLOWER in the replayed
-    graph, 12.32 vs 11.70 ms per step on the same box, at every group size: the side stream then lags without bound and
-    shares the chip with the main chain all the way through the large-map layers at the end of backward."""
-    jobs = _QUEUED.pop(dev, [])
-    if JOIN_EACH_GROUP:
-        if _INFLIGHT.get(dev):
-            cur.wait_stream(side)
-        _INFLIGHT[dev] = jobs               # the previous group's inputs may be reused from here on
-    else:
-        _INFLIGHT.setdefault(dev, []).extend(jobs)
-    if jobs:
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            for _, fn in jobs:
-                fn()
+@contextlib.contextmanager
+def lazy_param_grads(dev, enabled):
+    """Around a backward its caller owns from end to end (TrainStepRunner): with `enabled`, parameter gradients are deferred
+    (_param_grad) and valid only after this block.  It always clears the flag and joins, also when the body raises: the flag must
+    not leak into a later plain backward (AccumulateGrad would add to / clone a gradient the side stream has not written yet)."""
+    global LAZY_WGRAD_JOIN
+    LAZY_WGRAD_JOIN = bool(enabled)
+    try:
+        yield
+    finally:
+        LAZY_WGRAD_JOIN = False
+        join_wgrad_stream(dev)
 
 
-def defer_to_side(dev, keepalive, fn):
-    """In a LAZY_WGRAD_JOIN backward: queue `fn` (parameter-gradient work nothing downstream in backward reads; it
-    must write into tensors allocated by the caller) for the side stream and return True; `keepalive` holds its
-    inputs until the join after it ran.  Otherwise return False (the caller runs it inline)."""
-    if not (LAZY_WGRAD_JOIN and OVERLAP_WGRAD and dev.type == "cuda"):
-        return False
-    side = side_stream(dev)
-    q = _QUEUED.setdefault(dev, [])
-    q.append((keepalive, fn))
-    if len(q) >= WGRAD_GROUP:
-        _issue_wgrads(dev, torch.cuda.current_stream(dev), side)
-    return True
+def _param_grad(dev, shape, dtype, keepalive, run):
+    """A parameter gradient that nothing downstream in backward reads: `run(out)` writes it into `out`, on the side
+    stream at a later sync point when the device's SideQueue takes it (then `keepalive`, the inputs of `run`, live
+    until the join after it ran and the result is valid only after join_wgrad_stream()), else right here."""
+    out = torch.empty(shape, dtype=dtype, device=dev)
+    q = _side_queue(dev)
+    if q is None or not q.defer(keepalive, lambda: run(out)):
+        run(out)
+    # a second tensor object on the same storage: autograd's AccumulateGrad clones a gradient it cannot steal
+    # (use count > 1), and that clone would read `out` before the side stream has written it
+    return out.detach()
 
 
 def _wgrad_overlapped(x, dy, k, stride, w_dtype, dgrad_fn):
-    """(dx, dw) of a dense conv.  The two gradients are independent: the weight gradient is issued on a side HIP
-    stream (fork after dy is ready, join before returning), so on the small maps -- kernels of 100-400 workgroups on
-    a 256-CU chip -- the two run side by side; inside a captured step this becomes a fork/join in the hipGraph.
-    A cross-stream sync point costs ~10 us of idle GPU in the replayed graph (tools/trace_gaps.py).  With
-    LAZY_WGRAD_JOIN the join of a layer is taken at the fork of a LATER conv's backward (the side stream has long
-    finished by then) and WGRAD_GROUP convs share one sync point; x and dy of queued / running weight gradients are
-    kept alive until that join, and dw is valid only after join_wgrad_stream()."""
+    """(dx, dw) of a dense conv.  The two gradients are independent: the weight gradient is issued on a side HIP stream (fork
+    after dy is ready, join before returning), so on the small maps -- kernels of 100-400 workgroups on a 256-CU chip -- the two
+    run side by side; inside a captured step this becomes a fork/join in the hipGraph.  A cross-stream sync point costs ~10 us
+    of idle GPU in the replayed graph (tools/trace_gaps.py).  With LAZY_WGRAD_JOIN (lazy_param_grads) the weight gradient goes
+    through _param_grad: the join of a layer is taken at the fork of a LATER conv's backward (SideQueue.sync: the side stream
+    has long finished by then) and WGRAD_GROUP convs share one sync point."""
     if not (OVERLAP_WGRAD and x.is_cuda):
         return dgrad_fn(), ops.conv_wgrad(x, dy, k, stride, w_dtype)
     dev = x.device
-    cur, side = torch.cuda.current_stream(dev), side_stream(dev)
     if LAZY_WGRAD_JOIN:
-        dw = torch.empty((dy.shape[1], x.shape[1], k, k), dtype=w_dtype, device=dev)
-        fn = lambda: ops.conv_wgrad(x, dy, k, stride, dw.dtype, out=dw)
-        if not defer_to_side(dev, (x, dy), fn):
-            fn()
-        # a second tensor object on the same storage: autograd's AccumulateGrad clones a gradient it cannot steal
-        # (use count > 1), and that clone would read dw before the side stream has written it
-        return dgrad_fn(), dw.detach()
+        dw = _param_grad(dev, (dy.shape[1], x.shape[1], k, k), w_dtype, (x, dy),
+                         lambda out: ops.conv_wgrad(x, dy, k, stride, out.dtype, out=out))
+        return dgrad_fn(), dw
+    cur, side = torch.cuda.current_stream(dev), side_stream(dev)
     side.wait_stream(cur)
     with torch.cuda.stream(side):
         dw = ops.conv_wgrad(x, dy, k, stride, w_dtype)
@@ -148,21 +193,6 @@ def _wgrad_overlapped(x, dy, k, stride, w_dtype, dgrad_fn):
     cur.wait_stream(side)
     dw.record_stream(cur)           # allocated on the side stream, consumed (optimizer / reducer) on this one
     return dx, dw
-
-
-def join_wgrad_stream(device):
-    """End of a LAZY_WGRAD_JOIN backward: issue what is still queued and wait for the side stream."""
-    device = torch.device(device)
-    if device.index is None and device.type == "cuda":
-        device = torch.device("cuda", torch.cuda.current_device())
-    side = _SIDE.get(device)
-    if side is None:
-        return
-    cur = torch.cuda.current_stream(device)
-    _issue_wgrads(device, cur, side)
-    if _INFLIGHT.get(device):
-        cur.wait_stream(side)
-    _INFLIGHT[device] = []
 
 
 class BnArena:
@@ -195,8 +225,8 @@ class ResLink:
     consumers are those two convs.
 
     `fan=True` (see `fan2`) makes the protocol symmetric for ANY two consumers of an alias: whichever backward runs
-    first leaves its gradient in `dres` (and returns it to autograd), the second ADDS its own into that tensor in its
-    kernel epilogue and returns None -- autograd never sums, no extra pass over the gradient."""
+    first leaves its gradient here (`leave`, and returns it to autograd), the second ADDS its own into that tensor (`left`) in
+    its kernel epilogue and returns None -- autograd never sums, no extra pass over the gradient.  See `_fan_bwd`."""
     __slots__ = ("dres", "fan", "chunk")
 
     def __init__(self, fan=False):
@@ -204,12 +234,28 @@ class ResLink:
         self.fan = fan
         self.chunk = None           # ChunkLink of an enclosing C3K2 whose chunk half this alias is (see ChunkLink)
 
-    def usable(self, shape, dtype):
-        """The gradient left by the first consumer, if the second can accumulate into it."""
+    def left(self, shape, dtype):
+        """The gradient the other consumer left, if this one can accumulate into it."""
         d = self.dres
-        if d is None or tuple(d.shape) != tuple(shape) or d.dtype != dtype or not ops.is_nhwc(d):
-            return None
-        return d
+        return d if (d is not None and tuple(d.shape) == tuple(shape) and d.dtype == dtype and ops.is_nhwc(d)) else None
+
+    def leave(self, g):                 # for the other consumer to add to
+        self.dres = g
+
+
+def _fan_bwd(link, shape, dtype, run, leaves=True):
+    """THE fan-in rule.  Gradient of one consumer of a linked alias: `run(acc_into)` computes it, added to the gradient the other
+    consumer left when that one came first (returns None: nothing for autograd to add), else left in the link for the other one.
+    `leaves=False`: the second half of Residual's one-way link (conv1 adds into what conv2 left and leaves nothing itself)."""
+    if link is None:
+        return run(None)
+    into = link.left(shape, dtype)
+    g = run(into)
+    if into is not None:
+        return None
+    if leaves:
+        link.leave(g)
+    return g
 
 
 CHUNK_LINK = os.environ.get("YOLO_CHUNK_LINK", "1") == "1"     # 0: A/B runs
@@ -218,14 +264,32 @@ CHUNK_LINK = os.environ.get("YOLO_CHUNK_LINK", "1") == "1"     # 0: A/B runs
 class ChunkLink:
     """C3K2's second chunk half feeds the concat (gradient = a slice of the concat's gradient, `dst`, known as soon as
     CatInto.backward ran) AND the first chained block.  The block's entry convs add their data gradients straight into
-    `dst` -- a Residual's conv1 together with the skip gradient (`ops.conv_dgrad(acc_into=dst, acc2=skip gradient)`), a
-    C3K's two 1x1 convs one after the other -- and set `done`; Chunk2.backward then has nothing left to accumulate
-    (one pass over the gradient less per C3K2)."""
+    `dst` (`absorb`) and set `done`; Chunk2.backward then has nothing left to accumulate (one pass over the gradient
+    less per C3K2)."""
     __slots__ = ("dst", "done")
 
     def __init__(self):
         self.dst = None
         self.done = False
+
+    def absorb(self, link, shape, dtype, stride, run):
+        """Data gradient of an entry conv whose input alias carries `link`: `run(acc_into, acc2)` adds it into `dst` and True comes
+        back -- a C3K's two 1x1 convs one after the other (fan link: the first leaves `dst` in it, the second finds it there), a
+        Residual's conv1 together with the skip gradient conv2 left (acc2).  False: the caller computes it the plain way."""
+        dst = self.dst
+        if dst is None or stride != 1 or tuple(dst.shape) != tuple(shape) or dst.dtype != dtype or not ops.is_nhwc(dst):
+            return False
+        into = link.left(shape, dtype)
+        if link.fan:
+            run(into if into is not None else dst, None)
+            if into is None:
+                link.leave(dst)
+        elif into is not None:
+            run(dst, into)
+        else:
+            return False
+        self.done = True
+        return True
 
 
 class Alias(torch.autograd.Function):
@@ -244,26 +308,16 @@ class Alias(torch.autograd.Function):
         return g, None
 
 
-class Stash(torch.autograd.Function):
+class Stash(Alias):
     """Handle on an alias for a consumer that has no accumulating epilogue of its own (a concat slice, another fan-out):
     its gradient goes into the link for the other consumer to add to; if the other consumer came first, it is added to
     that one here (one HIP pass)."""
 
     @staticmethod
-    def forward(ctx, x, link):
-        ctx.link = link
-        return _fresh(x)
-
-    @staticmethod
     def backward(ctx, g):
-        link = ctx.link
         g = _as_nhwc(g, g.dtype)
-        first = link.usable(g.shape, g.dtype)
-        if first is None:
-            link.dres = g
-            return g, None
-        ops.copy_channels(g, first, accumulate=True)
-        return None, None
+        add = lambda into: g if into is None else ops.copy_channels(g, into, accumulate=True)
+        return _fan_bwd(ctx.link, g.shape, g.dtype, add), None
 
 
 def fan2(x):
@@ -310,24 +364,79 @@ def fanout(x, k):
     return Fanout.apply(x, k)
 
 
+def _on_fwd_stream(forward):
+    """A Function's forward (a static method) whose kernels are launched on FWD_STREAM when that is set, while autograd
+    still sees the node on the current stream (its backward then runs on the current stream; see Head.forward)."""
+    def on_stream(ctx, *args):
+        if FWD_STREAM is not None:
+            with torch.cuda.stream(FWD_STREAM):
+                return forward(ctx, *args)
+        return forward(ctx, *args)
+    return staticmethod(on_stream)
+
+
+def _bn_act_grads(dout, y, saved, act, training, acc_b):
+    """(dy, dgamma, dbeta): batch statistics with the sums in the arena slice `acc_b` / by the two-level reduction, running ones."""
+    scale, shift, mean, invstd, gamma = saved
+    if training and acc_b is not None:
+        return ops.bn_act_bwd_train(dout, y, scale, shift, mean, invstd, gamma, act, acc_b)
+    if training:
+        return ops.bn_act_bwd(dout, y, scale, shift, mean, invstd, gamma, act)
+    return ops.bn_act_bwd_eval(dout, y, scale, shift, act), None, None
+
+
+def _stem_grads(x, weight, dy, fused):
+    """dw of the stem conv (the image takes no gradient); x is the fp32 image (fused) or the unfolded column tensor."""
+    def run(out=None):
+        if fused:
+            return ops.stem_wgrad(x, dy, weight.dtype, out)
+        return ops.stem_unpack_wgrad(ops.conv_wgrad(x, dy, 1, 1, torch.float32), weight.dtype, out)
+    lazy = x.is_cuda and LAZY_WGRAD_JOIN
+    return _param_grad(x.device, weight.shape, weight.dtype, (x, dy), run) if lazy else run()
+
+
+def _dw_grads(x, weight, dy, xshape, link, want_dx, want_dw):
+    """(dx, dw) of a depthwise 3x3 conv; `link`: the fan link of its input alias, if any."""
+    dx = dw = None
+    if want_dx:
+        dx = _fan_bwd(link, xshape, dy.dtype, lambda into: ops.dw_dgrad(dy, _f32(weight).reshape(-1, 9), acc_into=into))
+    if want_dw:
+        if weight.dtype == torch.float32 and x.is_cuda and LAZY_WGRAD_JOIN:
+            dw = _param_grad(x.device, (x.shape[1], 1, 3, 3), torch.float32, (x, dy), lambda out: ops.dw_wgrad(x, dy, out=out))
+        else:
+            dw = ops.dw_wgrad(x, dy).to(weight.dtype)
+    return dx, dw
+
+
+def _dense_dgrad(weight, dy, xshape, k, stride, link):
+    """dx of a dense conv: into the concat gradient's slice where an enclosing C3K2 asks for it (ChunkLink.absorb), else by the
+    fan-in rule: added to the residual gradient conv2's backward left (Residual's link) / to what the alias' other consumer left."""
+    (n, cin, h, w), T = xshape, dy.dtype
+    def run(acc_into, acc2=None):
+        return ops.conv_dgrad(dy, ops.pack_weights(weight, k, stride, 1, T), cin, h, w, k, stride, acc_into=acc_into, acc2=acc2)
+    if link is not None and link.chunk is not None and link.chunk.absorb(link, xshape, T, stride, run):
+        return None
+    return _fan_bwd(link, xshape, T, run, leaves=link is not None and link.fan)
+
+
+def _dense_grads(x, weight, dy, xshape, k, stride, link, want_dx, want_dw):
+    """(dx, dw) of a dense conv; `link`: the link of its input alias, if any."""
+    if want_dx and want_dw:
+        return _wgrad_overlapped(x, dy, k, stride, weight.dtype, lambda: _dense_dgrad(weight, dy, xshape, k, stride, link))
+    if want_dx:
+        return _dense_dgrad(weight, dy, xshape, k, stride, link), None
+    return None, (ops.conv_wgrad(x, dy, k, stride, weight.dtype) if want_dw else None)
+
+
 class ConvBnAct(torch.autograd.Function):
     """act(BN(conv(x))) (+ residual).  Reference: Conv.forward, src/model/model_blocks.py:31-34; the
     residual adds of Residual/PSABlock (:62, :223-224) ride in the same epilogue.
     groups is 1 or C (depthwise 3x3).  Training: the conv epilogue accumulates the batch statistics (no
     separate pass over y); the backward uses the deterministic two-level reduction."""
 
-    @staticmethod
-    def forward(ctx, *args):
-        # FWD_STREAM: launch this node's kernels on another stream while autograd still sees it on the current one
-        # (its backward then runs on the current stream; see Head.forward)
-        if FWD_STREAM is not None:
-            with torch.cuda.stream(FWD_STREAM):
-                return ConvBnAct._forward(ctx, *args)
-        return ConvBnAct._forward(ctx, *args)
-
-    @staticmethod
-    def _forward(ctx, x, weight, gamma, beta, res, bufs, k, stride, depthwise, act, training, momentum, eps, out=None,
-                 res_link=None):
+    @_on_fwd_stream
+    def forward(ctx, x, weight, gamma, beta, res, bufs, k, stride, depthwise, act, training, momentum, eps, out=None,
+                res_link=None):
         ctx.res_link = res_link
         T = compute_dtype(x, weight)
         cout = weight.shape[0]
@@ -388,99 +497,28 @@ class ConvBnAct(torch.autograd.Function):
         x, weight, y = ctx.saved_tensors[:3]
         T = y.dtype
         dout = _as_nhwc(dout, T)
-        scale, shift, mean, invstd, gamma = ctx.saved_tensors[3:]
-        acc_b = ctx.acc_b
-        if training and acc_b is not None:
-            dy, dgamma, dbeta = ops.bn_act_bwd_train(dout, y, scale, shift, mean, invstd, gamma, act, acc_b)
-        elif training:
-            dy, dgamma, dbeta = ops.bn_act_bwd(dout, y, scale, shift, mean, invstd, gamma, act)
-        else:
-            dy, dgamma, dbeta = ops.bn_act_bwd_eval(dout, y, scale, shift, act), None, None
-        dx = dw = None
-        n, cin, h, w = xshape
+        dy, dgamma, dbeta = _bn_act_grads(dout, y, ctx.saved_tensors[3:], act, training, ctx.acc_b)
+        want_dx, want_dw = ctx.needs_input_grad[:2]
+        link = ctx.res_link if not has_res else None
         if stem:
-            if ctx.needs_input_grad[1]:
-                def stem_dw(out=None):          # x is the fp32 image (fused) or the unfolded column tensor
-                    if ctx.stem_fused:
-                        return ops.stem_wgrad(x, dy, weight.dtype, out)
-                    return ops.stem_unpack_wgrad(ops.conv_wgrad(x, dy, 1, 1, torch.float32), weight.dtype, out)
-                if x.is_cuda and LAZY_WGRAD_JOIN:
-                    dwb = torch.empty(weight.shape, dtype=weight.dtype, device=x.device)
-                    if not defer_to_side(x.device, (x, dy), lambda: stem_dw(dwb)):
-                        stem_dw(dwb)
-                    dw = dwb.detach()
-                else:
-                    dw = stem_dw()
+            dx, dw = None, (_stem_grads(x, weight, dy, ctx.stem_fused) if want_dw else None)
         elif depthwise:
-            if ctx.needs_input_grad[0]:
-                link = ctx.res_link if (ctx.res_link is not None and ctx.res_link.fan and not has_res) else None
-                into = link.usable((n, cin, h, w), T) if link is not None else None
-                dx = ops.dw_dgrad(dy, _f32(weight).reshape(weight.shape[0], 9), acc_into=into)
-                if into is not None:
-                    dx = None                                   # already inside the gradient the first consumer returned
-                elif link is not None:
-                    link.dres = dx
-            if ctx.needs_input_grad[1]:
-                if weight.dtype == torch.float32 and x.is_cuda and LAZY_WGRAD_JOIN:
-                    dwb = torch.empty((weight.shape[0], 1, 3, 3), dtype=torch.float32, device=x.device)
-                    fn = lambda: ops.dw_wgrad(x, dy, out=dwb)
-                    if not defer_to_side(x.device, (x, dy), fn):
-                        fn()
-                    dw = dwb.detach()
-                else:
-                    dw = ops.dw_wgrad(x, dy).to(weight.dtype)
+            dx, dw = _dw_grads(x, weight, dy, xshape, link if (link is not None and link.fan) else None, want_dx, want_dw)
         else:
-            link = ctx.res_link if not has_res else None
-            # the residual gradient conv2's backward left / the gradient the alias' other consumer left (fan link)
-            into = link.usable((n, cin, h, w), T) if link is not None else None
-
-            def dgrad():
-                cl = link.chunk if link is not None else None
-                dst = cl.dst if cl is not None else None
-                if dst is not None and stride == 1 and tuple(dst.shape) == (n, cin, h, w) and dst.dtype == T and ops.is_nhwc(dst):
-                    wb = ops.pack_weights(weight, k, stride, 1, T)
-                    if link.fan:                            # C3K entry: both 1x1 convs add into the concat's slice
-                        ops.conv_dgrad(dy, wb, cin, h, w, k, stride, acc_into=into if into is not None else dst)
-                        if into is None:
-                            link.dres = dst
-                        cl.done = True
-                        return None
-                    if into is not None:                    # Residual entry: slice += skip gradient + this data gradient
-                        ops.conv_dgrad(dy, wb, cin, h, w, k, stride, acc_into=dst, acc2=into)
-                        cl.done = True
-                        return None
-                r = ops.conv_dgrad(dy, ops.pack_weights(weight, k, stride, 1, T), cin, h, w, k, stride, acc_into=into)
-                if into is not None:
-                    return None                             # already inside the gradient autograd holds for x
-                if link is not None and link.fan:
-                    link.dres = r                           # first of the two consumers: the other adds to this
-                return r
-            if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-                dx, dw = _wgrad_overlapped(x, dy, k, stride, weight.dtype, dgrad)
-            elif ctx.needs_input_grad[0]:
-                dx = dgrad()
-            elif ctx.needs_input_grad[1]:
-                dw = ops.conv_wgrad(x, dy, k, stride, weight.dtype)
+            dx, dw = _dense_grads(x, weight, dy, xshape, k, stride, link, want_dx, want_dw)
         if dgamma is None or not ctx.needs_input_grad[2]:      # (the kernels wrote them in the parameters' own dtype)
             dgamma = dbeta = None
         dres = dout if (has_res and ctx.needs_input_grad[4]) else None
         if has_res and ctx.res_link is not None and not ctx.res_link.fan:
-            ctx.res_link.dres = dres
+            ctx.res_link.leave(dres)
         return dx, dw, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None
 
 
 class ConvBias(torch.autograd.Function):
     """Plain dense conv + bias: the head's final nn.Conv2d 1x1 (src/model/head.py:50,60)."""
 
-    @staticmethod
-    def forward(ctx, *args):
-        if FWD_STREAM is not None:
-            with torch.cuda.stream(FWD_STREAM):
-                return ConvBias._forward(ctx, *args)
-        return ConvBias._forward(ctx, *args)
-
-    @staticmethod
-    def _forward(ctx, x, weight, bias, k, stride):
+    @_on_fwd_stream
+    def forward(ctx, x, weight, bias, k, stride):
         T = compute_dtype(x, weight)
         x = _as_nhwc(x, T)
         cout = weight.shape[0]
@@ -499,23 +537,15 @@ class ConvBias(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = ops.conv_dgrad(dy, ops.pack_weights(weight, k, stride, 1, x.dtype), cin, h, w, k, stride)
-        lazy = x.is_cuda and LAZY_WGRAD_JOIN
         if ctx.needs_input_grad[1]:
-            if lazy:
-                dwb = torch.empty(weight.shape, dtype=weight.dtype, device=x.device)
-                fn = lambda: ops.conv_wgrad(x, dy, k, stride, dwb.dtype, out=dwb)
-                if not defer_to_side(x.device, (x, dy), fn):
-                    fn()
-                dw = dwb.detach()
+            if x.is_cuda and LAZY_WGRAD_JOIN:
+                dw = _param_grad(x.device, weight.shape, weight.dtype, (x, dy),
+                                 lambda out: ops.conv_wgrad(x, dy, k, stride, out.dtype, out=out))
             else:
                 dw = ops.conv_wgrad(x, dy, k, stride, weight.dtype)
         if bdtype is not None and ctx.needs_input_grad[2]:
-            if lazy and bdtype == torch.float32:
-                dbb = torch.empty(weight.shape[0], dtype=torch.float32, device=x.device)
-                fnb = lambda: ops.channel_sum(dy, out=dbb)
-                if not defer_to_side(x.device, (dy,), fnb):
-                    fnb()
-                db = dbb.detach()
+            if x.is_cuda and LAZY_WGRAD_JOIN and bdtype == torch.float32:
+                db = _param_grad(x.device, weight.shape[0], torch.float32, (dy,), lambda out: ops.channel_sum(dy, out=out))
             else:
                 db = ops.channel_sum(dy).to(bdtype)
         return dx, dw, db, None, None
@@ -596,25 +626,12 @@ class Cat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        dout = _as_nhwc(dout, dout.dtype)
-        grads, off = [], 0
-        for c in ctx.cs:
-            grads.append(dout[:, off:off + c])
-            off += c
-        return tuple(grads)
+        return tuple(_channel_slices(_as_nhwc(dout, dout.dtype), ctx.cs))
 
 
-def _fan_bwd(link, shape, dtype, run):
-    """Gradient of one of the two consumers of a fan2 alias: `run(acc_into)` computes it, added to the other consumer's
-    gradient when that one came first (returns None: nothing for autograd to add), else left in the link."""
-    if link is None:
-        return run(None)
-    into = link.usable(shape, dtype)
-    g = run(into)
-    if into is not None:
-        return None
-    link.dres = g
-    return g
+def _channel_slices(t, cs):
+    offs = [sum(cs[:i]) for i in range(len(cs))]
+    return [t[:, off:off + c] for off, c in zip(offs, cs)]
 
 
 def _fresh(t):
@@ -656,11 +673,7 @@ class CatInto(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        dout = _as_nhwc(dout, dout.dtype)
-        grads, off = [None], 0
-        for c in ctx.cs:
-            grads.append(dout[:, off:off + c])
-            off += c
+        grads = [None] + _channel_slices(_as_nhwc(dout, dout.dtype), ctx.cs)
         if ctx.link is not None:
             cl, index = ctx.link
             cl.dst, cl.done = grads[1 + index], False
@@ -825,51 +838,38 @@ UNIT_LOSS_SEED = False
 LOSS_SCALE = None
 
 
-class DflQflLoss(torch.autograd.Function):
+class _FusedLoss(torch.autograd.Function):
+    """Value and gradient of a loss from one fused pass of a leaf; the backward only applies the incoming gradient."""
+
+    @staticmethod
+    def run(ctx, leaf, preds, anchors, strides, packed, nc, hyper):             # packed = (gt, gt_off, gt_img, n_gt)
+        want = ctx.needs_input_grad[0]
+        out, ctx.dpreds, _ = leaf(preds.contiguous(), anchors, strides, *packed, nc, *hyper, want, LOSS_SCALE if want else None)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_scalars):
+        dpreds, ctx.dpreds = ctx.dpreds, None
+        # a seed of exactly 1.0 (see UNIT_LOSS_SEED) leaves every 16-bit value as it is: no pass over dpreds
+        if dpreds is not None and not UNIT_LOSS_SEED:
+            ops.scale_inplace(dpreds, g_total.reshape(1).float())
+        return (dpreds,) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+class DflQflLoss(_FusedLoss):
     """YoloDFLQFLoss value and gradient from one fused pass (src/model/losses.py:140-281).
     Returns (total, scalars[3]); scalars = (total, mean_dfl, mean_cls) detached."""
 
     @staticmethod
     def forward(ctx, preds, anchors, strides, packed, nc, lambda_dfl, lambda_cls):
-        gt, gt_off, gt_img, n_gt = packed
-        want = ctx.needs_input_grad[0]
-        out, dpreds, _ = ops.loss_fwd_bwd(preds.contiguous(), anchors, strides, gt, gt_off, gt_img, n_gt, nc,
-                                          lambda_dfl, lambda_cls, want, LOSS_SCALE if want else None)
-        ctx.dpreds = dpreds
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
-
-    @staticmethod
-    def backward(ctx, g_total, _g_scalars):
-        dpreds = ctx.dpreds
-        ctx.dpreds = None
-        if dpreds is None:
-            return (None,) * 7
-        if not UNIT_LOSS_SEED:      # a seed of exactly 1.0 (see UNIT_LOSS_SEED) leaves every 16-bit value as it is: no pass over dpreds
-            ops.scale_inplace(dpreds, g_total.reshape(1).float())
-        return dpreds, None, None, None, None, None, None
+        return _FusedLoss.run(ctx, ops.loss_fwd_bwd, preds, anchors, strides, packed, nc, (lambda_dfl, lambda_cls))
 
 
-class TalLoss(torch.autograd.Function):
+class TalLoss(_FusedLoss):
     """YoloTALoss value and gradient from one fused pass (csrc/loss_tal.hip).
     Returns (total, scalars[4]); scalars = (total, box, cls, dfl) detached.  LOSS_SCALE and UNIT_LOSS_SEED as in DflQflLoss."""
 
     @staticmethod
     def forward(ctx, preds, anchors, strides, packed, nc, hyper):
-        gt, gt_off, gt_img, n_gt = packed
-        want = ctx.needs_input_grad[0]
-        out, dpreds, _ = ops.loss_tal_fwd_bwd(preds.contiguous(), anchors, strides, gt, gt_off, gt_img, n_gt, nc, *hyper,
-                                              want, LOSS_SCALE if want else None)
-        ctx.dpreds = dpreds
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
-
-    @staticmethod
-    def backward(ctx, g_total, _g_scalars):
-        dpreds = ctx.dpreds
-        ctx.dpreds = None
-        if dpreds is None:
-            return (None,) * 6
-        if not UNIT_LOSS_SEED:
-            ops.scale_inplace(dpreds, g_total.reshape(1).float())
-        return dpreds, None, None, None, None, None
+        return _FusedLoss.run(ctx, ops.loss_tal_fwd_bwd, preds, anchors, strides, packed, nc, hyper)

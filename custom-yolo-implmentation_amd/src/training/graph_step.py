@@ -173,38 +173,29 @@ class TrainStepRunner:
     def _stage_a(self, images, packed):
         """forward + loss + backward down to the stage cut (the whole backward when there is no cut)."""
         dev = images.device
-        cut = {}
+        cut, self._cut = {}, None           # left None if this raises: stage B will not run
         if self.staged:
             def at_cut(feats):
                 cut["out"] = list(feats)
                 cut["leaf"] = [t.detach().requires_grad_(True) for t in feats]
                 return cut["leaf"]
             self.model.stage_cut = at_cut
-        F_.LAZY_WGRAD_JOIN = self._lazy(dev)
+        cut["lazy"] = self._lazy(dev)       # decided once per step: after this stage the head's .grad fields are set
         F_.LOSS_SCALE = self.amp.scale if self.amp is not None else None
         try:
-            with torch.autocast(dev.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
-                preds, anchors, strides = self.model(images)
-                loss, ld = self.criterion(preds, packed, anchors, strides)
-            F_.LOSS_SCALE = None
-            # the loss tensor is the fused loss node's own output: the seed of backward() (ones) reaches it unchanged
-            F_.UNIT_LOSS_SEED = type(loss.grad_fn).__name__ == "DflQflLossBackward" and os.environ.get("YOLO_UNIT_SEED", "1") == "1"
-            loss.backward()
-        except BaseException:
-            # stage B will not run: the lazy-join flag must not leak into a later plain backward (AccumulateGrad would
-            # add to / clone a gradient the side stream has not written yet)
-            F_.LAZY_WGRAD_JOIN = False
-            self._cut = None
-            raise
+            with F_.lazy_param_grads(dev, cut["lazy"]):
+                with torch.autocast(dev.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
+                    preds, anchors, strides = self.model(images)
+                    loss, ld = self.criterion(preds, packed, anchors, strides)
+                F_.LOSS_SCALE = None
+                # the loss tensor is the fused loss node's own output: the seed of backward() (ones) reaches it unchanged
+                F_.UNIT_LOSS_SEED = type(loss.grad_fn).__name__ == "DflQflLossBackward" and os.environ.get("YOLO_UNIT_SEED", "1") == "1"
+                loss.backward()
         finally:
             F_.UNIT_LOSS_SEED = False
             F_.LOSS_SCALE = None
             if self.staged:
                 self.model.stage_cut = None
-            if not self.staged:
-                F_.LAZY_WGRAD_JOIN = False
-            if dev.type == "cuda":
-                F_.join_wgrad_stream(dev)
         self._cut = cut if self.staged else None
         return loss, ld
 
@@ -213,13 +204,9 @@ class TrainStepRunner:
         if self._cut is None:
             return
         cut, self._cut = self._cut, None
-        try:
+        with F_.lazy_param_grads(device, cut["lazy"]):
             pairs = [(o, l.grad) for o, l in zip(cut["out"], cut["leaf"]) if l.grad is not None]
             torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
-        finally:
-            F_.LAZY_WGRAD_JOIN = False
-            if device.type == "cuda":
-                F_.join_wgrad_stream(device)
 
     def _fwd_bwd(self, images, packed):
         loss, ld = self._stage_a(images, packed)
