@@ -1,6 +1,8 @@
 // AdamW step of ALL parameters in one launch.
 // torch.optim.AdamW semantics (decoupled weight decay, bias correction, eps added to sqrt(v)/sqrt(bc2)):
 //   p *= 1 - lr*wd;  m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// As computed (adam_elem): the decay and the subtraction are ONE fused multiply-add, p = fma(p, 1 - lr*wd, -step), so the
+// decayed parameter is never rounded on its own; sqrt is the hardware root (within 1 ulp, not correctly rounded).
 // A device job table lists (param, grad, exp_avg, exp_avg_sq, numel) per tensor; one workgroup owns one 4096-element
 // chunk of one tensor (job found once per workgroup).  Hyper-parameters and the step counter live in device memory so
 // a captured step follows a learning-rate schedule without recapture; GradScaler's scale / found_inf pair is
@@ -42,10 +44,20 @@ __device__ __forceinline__ void st_any(void* p, int dt, long i, float x) {
     else ((f16_t*)p)[i] = from_f<f16_t>(x);
 }
 
-// The update of ONE element, shared by the packet path and the any-dtype path: explicit fmaf / mul sequence, so that the
-// same (p, g, m, v) give the same bits whichever path a tensor takes (a low-precision gradient of an fp32 master goes
-// through the generic one; left to the compiler the two loops were contracted differently: 1-ulp differences between
-// the sharded runner and torch FSDP2 on the same gradients).
+// The update of ONE element, shared by the packet path and the any-dtype path, so that the same (p, g, m, v) give the
+// same bits whichever path a tensor takes (a low-precision gradient of an fp32 master goes through the generic one;
+// left to the compiler the two loops were contracted differently: 1-ulp differences between the sharded runner and
+// torch FSDP2 on the same gradients).  What the spelling does and does not pin: the two __fmaf_rn are fused
+// multiply-adds wherever they are inlined, and their addends, the root and the divisions are operations that the
+// compiler has nothing to contract with.  The LAST line is not pinned: without OCML_BASIC_ROUNDED_OPERATIONS
+// __fsub_rn(x, y) is x - y and __fmul_rn(x, y) is x * y, and under the default contraction p*decay - step is compiled
+// to ONE fused multiply-add on both paths (v_pk_fma_f32 with neg_lo / neg_hi on the addend in the packet loop,
+// v_fma_f32 with a negated addend in the any-dtype loop): one rounding for the decay and the subtraction together, the
+// decayed parameter is never rounded on its own.  That both loops agree there is the compiler's choice, held by
+// tests/test_gpu_adamw.py's bit-for-bit comparison of the two paths.  (Spelled as __fmaf_rn(p, decay, -step) the line
+// gives the same values but another instruction stream -- the negation moves into the step_size * m multiply -- so it
+// stays as it is.)  __fsqrt_rn is the hardware square root between two v_ldexp_f32, no correction step: within 1 ulp
+// (ISA manual), not correctly rounded.  tests/strict_optim.py counts these roundings and bounds every element by them.
 __device__ __forceinline__ void adam_elem(float& p, float gg, float& m, float& v, float b1, float omb1, float b2, float omb2,
                                           float step_size, float bc2s, float decay, float eps) {
     m = __fmaf_rn(b1, m, __fmul_rn(omb1, gg));
