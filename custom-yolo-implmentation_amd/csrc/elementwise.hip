@@ -2,6 +2,7 @@
 // backward, SPPF max-pool, nearest x2 upsample.  One 16-byte packet per lane wherever the channel
 // count allows it (guide: Guideline 13), fp32 arithmetic, fp32 statistics.
 #include "common.h"
+#include "bn_coef.h"
 
 namespace {
 
@@ -206,16 +207,7 @@ __global__ void k_add_n(AddSrcs s, T* __restrict__ dst, int ldd, long npix, int 
 // BatchNorm (+SiLU, +residual): per-channel reductions over pixels, finalizes, normalise / gradient passes.
 // The six kernels that touch every element share one row-strided pixel walk (rs_walk).
 // ---------------------------------------------------------------------------------------------
-// sigmoid for the BatchNorm + SiLU kernels: hardware reciprocal (1 ulp) instead of the IEEE division -- the division
-// expands to ~10 VALU instructions per element (v_div_scale x2, v_rcp, 4 fma, v_div_fmas, v_div_fixup) and these kernels
-// are co-limited by VALU issue (a wave64 op takes 4 cycles on the 16-lane SIMD): about a quarter of their instructions
-__device__ __forceinline__ float sigmoid_rcp(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
-__device__ __forceinline__ float act_grad(float z, int act) {
-    if (act == 0) return 1.f;
-    float s = sigmoid_rcp(z);
-    return s * (1.f + z * (1.f - s));
-}
+// (sigmoid_rcp and act_grad: bn_coef.h, shared with the stem's one-pass backward)
 __device__ __forceinline__ float act_fwd(float z, int act) { return act == 0 ? z : z * sigmoid_rcp(z); }
 
 // Row-strided walk: a workgroup is rpb = TPB / tpr pixel rows of tpr lanes; a thread keeps ONE channel group (cg: V
@@ -330,27 +322,7 @@ void k_channel_reduce(const T* __restrict__ y, int ldy, const T* __restrict__ do
 // its prologue.  Workgroup (0, y) also publishes mean / invstd / running statistics (forward) or
 // dgamma / dbeta (backward).
 // ---------------------------------------------------------------------------------------------
-// BatchNorm parameters (gamma, beta -> dgamma, dbeta) and buffers (running statistics) in their own element type:
-// fp32 under DDP / autocast, the low-precision parameter dtype under FSDP mixed precision, whose policy casts
-// parameters AND buffers (reference src/training/utils_train.py:84-89,146-153).  Read / written once per channel in
-// the prologues, arithmetic in fp32 / double as before, one rounding on the way out.
-struct PIn {
-    const void* p; int dt;
-    __device__ __forceinline__ float ld(int i) const {
-        return dt == YOLO_F32 ? ((const float*)p)[i] : dt == YOLO_BF16 ? (float)((const bf16_t*)p)[i] : (float)((const f16_t*)p)[i];
-    }
-};
-struct PIo {
-    void* p; int dt;
-    __device__ __forceinline__ float ld(int i) const {
-        return dt == YOLO_F32 ? ((const float*)p)[i] : dt == YOLO_BF16 ? (float)((const bf16_t*)p)[i] : (float)((const f16_t*)p)[i];
-    }
-    __device__ __forceinline__ void st(int i, float v) const {
-        if (dt == YOLO_F32) ((float*)p)[i] = v; else if (dt == YOLO_BF16) ((bf16_t*)p)[i] = (bf16_t)v; else ((f16_t*)p)[i] = (f16_t)v;
-    }
-};
-static inline bool pdt_ok(int dt) { return dt == YOLO_F32 || dt == YOLO_BF16 || dt == YOLO_F16; }
-
+// BatchNorm parameters and buffers travel in their own element type: PIn / PIo of bn_coef.h.
 constexpr int BN_REPL = 8;
 
 // per-channel constants of a workgroup's cw = tpr*V channels (dynamic LDS): [2][cw] scale, shift in the forward kernel,
@@ -403,22 +375,8 @@ __device__ __forceinline__ void bn_fwd_publish(const BnFwdCoef& k, int c, float 
         rvar.st(c, (1.f - momentum) * rvar.ld(c) + momentum * k.unbiased);
     }
 }
-// Backward: (sum dz, sum dz*y) in double -> dbeta = sum dz, dgamma = sum dz*yhat = invstd*(sum dz*y - mean*sum dz), and
-// dy = k0*(dz - c1 - yhat*c2), yhat = (y-mean)*invstd  ==  A*dz + B*y + D  (three constants per channel)
-struct BnBwdCoef { float dbeta, dgamma, A, B, D; };
-__device__ __forceinline__ BnBwdCoef bn_bwd_coef(double s, double q, float count, const PIn& gamma, const float* __restrict__ mean,
-                                                 const float* __restrict__ invstd, int c) {
-    const double is = invstd[c], mu = mean[c];
-    q = is * (q - mu * s);
-    const double k0 = (double)gamma.ld(c) * is, c1 = s / count, c2 = q / count;
-    BnBwdCoef k;
-    k.dbeta = (float)s;
-    k.dgamma = (float)q;
-    k.A = (float)k0;
-    k.B = (float)(-k0 * c2 * is);
-    k.D = (float)(-k0 * c1 + k0 * c2 * mu * is);
-    return k;
-}
+// Backward: (sum dz, sum dz*y) in double -> dbeta, dgamma and the three constants of dy = A*dz + B*y + D: bn_bwd_coef of
+// bn_coef.h.
 
 // acc[8][2][C] -> mean, invstd, scale, shift (+ running statistics): one thread per channel, 16 loads
 __global__ void k_bn_finalize_acc(const float* __restrict__ acc, float count, int C, const void* __restrict__ gamma_,

@@ -5,6 +5,7 @@
 // as 1x1 convolutions on the MFMA kernels.  k = ci*9 + kh*3 + kw is exactly the OIHW flattening, so
 // weights and weight gradients are plain [Cout][27] views padded to 32.
 #include "common.h"
+#include "bn_coef.h"
 #include "conv_dev.h"
 
 namespace {
@@ -364,6 +365,273 @@ int launch_stem_wgrad(const float* img, const void* dy, int ldy, float* part, in
     return YOLO_LAUNCH_CHECK();
 }
 
+// ---- the stem's whole backward in ONE pass over (dout, y, image) --------------------------------------------------
+// The stem takes no input gradient: the only consumer of BatchNorm's dy = A*dz + B*y + D (bn_bwd_coef) is the weight
+// gradient, and there the channel co is an OUTPUT index, so the three per-channel constants factor out of the pixel sum:
+//     dW[co][k] = A_co * G1[co][k] + B_co * G2[co][k] + D_co * G3[k]
+//     G1 = sum_p dz[p][co] X[p][k],  G2 = sum_p y[p][co] X[p][k],  G3 = sum_p X[p][k] over the pixels that exist
+// None of the sums needs A, B, D, which depend on (sum dz, sum dz*y) only: one kernel -- k_stem_wgrad's tile, staged image
+// rows, grid-stride walk and one partial block per workgroup -- forms dz = dout * act'(y*scale + shift) in fp32, adds dz and
+// dz*y into per-thread channel sums (unrounded, as channel_sums MODE 1 does), rounds dz once to T into one LDS tile, keeps y
+// as stored in a second, and runs two MFMA accumulations per fragment on the same unfold fragments; G3 is a VALU sum of those
+// fragments under the pixel's validity (a pixel past the row / image end still has taps inside the image).  dy is never
+// formed, written or read.  The next tile's dout / y chunks are loaded while the current tile's fragments are multiplied.
+// Partial block of a workgroup (fp32): G1[Cout][32], G2[Cout][32], G3[32], sum dz[Cout], sum dz*y[Cout].
+constexpr int STEM_BN_SLABS = 512;                         // Cout = 32: 218 registers, two workgroups per CU on 256 CUs: one round
+constexpr long stem_bn_block(int cout) { return (long)cout * 64 + 32 + 2 * cout; }
+
+template <typename T, int CT, int ACT>
+__global__ __launch_bounds__(256) void k_stem_bn_wgrad(const float* __restrict__ img, const T* __restrict__ dout, int ldd,
+                                                       const T* __restrict__ y, int ldy, const float* __restrict__ scale,
+                                                       const float* __restrict__ shift, float* __restrict__ part, int N, int H,
+                                                       int W, int OH, int OW, long tiles) {
+    typedef mfma_ops<T> ops;
+    typedef typename ops::frag frag;
+    typedef pack_t<T, 8> chunk;
+    constexpr int LDY = stem_ldy(CT), COUT = 16 * CT, TILE = 2 * STEM_SEG * LDY;
+    // a thread keeps ONE 8-channel chunk (cpc) and walks pixels pl, pl + PPT, ...: its channel sums stay in registers
+    constexpr int CPP = COUT / 8, PPT = 256 / CPP, NP = (2 * STEM_SEG + PPT - 1) / PPT;
+    constexpr int RED = 17;                                  // row stride of the channel-sum exchange (16 values per thread)
+    static_assert((2 * COUT * 32 + 32 + 256 * RED) * sizeof(float) <= 2 * TILE * sizeof(T), "the sums reuse the two tiles");
+    __shared__ __attribute__((aligned(16))) float rows[3 * STEM_IR][STEM_ROWW + 7];
+    __shared__ __attribute__((aligned(16))) T zs[2 * TILE];      // [0, TILE): dz rounded to T; [TILE, 2 TILE): y as stored
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, c4 = 4 * (i16 & 3);
+    const int segs = (OW + STEM_SEG - 1) / STEM_SEG, ohp = (OH + 1) >> 1;
+    const int cpc = tid % CPP, pl = tid / CPP;
+    const bool mine = pl < PPT;                              // Cout = 48, 96: four threads hold no chunk
+    f32x4 acc1[CT][2], acc2[CT][2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) acc1[ct][nt] = acc2[ct][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float g3[2] = {0.f, 0.f}, s[8], q[8], sc[8], sh[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        s[j] = q[j] = 0.f;
+        sc[j] = scale[cpc * 8 + j];
+        sh[j] = shift[cpc * 8 + j];
+    }
+    int krow[2], kcol[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int k = nt * 16 + i16, ci = k / 9, r3 = k / 3;
+        krow[nt] = k < 27 ? ci * STEM_IR + (r3 - ci * 3) : -1;
+        kcol[nt] = k - r3 * 3 + 3;
+    }
+    // dout and y of tile tl: 16-byte chunks, pixels past the row / image end are zeros (clamped addresses, no branch)
+    chunk dv[NP], yv[NP];
+    auto fetch = [&](long tl) {
+        const int seg = (int)(tl % segs);
+        const long t = tl / segs;
+        const int oh0 = (int)(t % ohp) * 2, n = (int)(t / ohp), ow0 = seg * STEM_SEG;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const int px = pl + k * PPT, j = px / STEM_SEG, p = px - j * STEM_SEG;
+            const bool ok = mine && px < 2 * STEM_SEG && oh0 + j < OH && ow0 + p < OW;
+            const long pix = ((long)n * OH + (ok ? oh0 + j : 0)) * OW + (ok ? ow0 + p : 0);
+            dv[k] = load_raw<T, 8>(dout + pix * ldd + cpc * 8);
+            yv[k] = load_raw<T, 8>(y + pix * ldy + cpc * 8);
+            if (!ok) dv[k] = yv[k] = chunk{};
+        }
+    };
+    if (blockIdx.x < tiles) fetch(blockIdx.x);
+    for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
+        const int seg = (int)(tl % segs);
+        const long t = tl / segs;
+        const int oh0 = (int)(t % ohp) * 2, n = (int)(t / ohp);
+        const int ow0 = seg * STEM_SEG, iw0 = 2 * ow0 - 1;
+        __syncthreads();                                    // the previous tile's fragments have been read
+        constexpr int RPW = (3 * STEM_IR + 3) / 4;            // a wave's image row segments: in flight during the dz arithmetic
+        float4 v[RPW];
+        float edge[RPW];
+        const bool w4 = (W & 3) == 0;
+        if (w4) {
+            const int c = lane * 4;
+#pragma unroll
+            for (int k = 0; k < RPW; ++k) {
+                const int r = wave + 4 * k, rr = r < 3 * STEM_IR ? r : 0;
+                const int ci = rr / STEM_IR, ir = rr - ci * STEM_IR;
+                const int ih = 2 * oh0 + ir - 1;
+                const bool rok = ih >= 0 && ih < H;
+                const float* src = img + (((long)n * 3 + ci) * H + (rok ? ih : 0)) * (long)W + 2 * ow0;
+                const bool cok = 2 * ow0 + c < W;
+                v[k] = *reinterpret_cast<const float4*>(src + (cok ? c : 0));
+                if (!(rok && cok)) v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                edge[k] = (lane == 0 && ow0 > 0) ? src[-1] : 0.f;
+                if (!rok) edge[k] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const int px = pl + k * PPT;
+            if (mine && px < 2 * STEM_SEG) {
+                float d[8], a[8];
+                unpack<T, 8>(dv[k], d);
+                unpack<T, 8>(yv[k], a);
+                chunk z;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float dz = d[j] * act_grad(a[j] * sc[j] + sh[j], ACT);
+                    s[j] += dz;
+                    q[j] += dz * a[j];
+                    z.v[j] = from_f<T>(dz);
+                }
+                *reinterpret_cast<chunk*>(zs + px * LDY + cpc * 8) = z;
+                *reinterpret_cast<chunk*>(zs + TILE + px * LDY + cpc * 8) = yv[k];
+            }
+        }
+        if (w4) {
+            const int c = lane * 4;
+#pragma unroll
+            for (int k = 0; k < RPW; ++k) {
+                const int r = wave + 4 * k;
+                if (r < 3 * STEM_IR) {
+                    *reinterpret_cast<float4*>(&rows[r][4 + c]) = v[k];
+                    if (lane == 0) rows[r][3] = edge[k];
+                }
+            }
+        } else {
+            for (int idx = tid; idx < 3 * STEM_IR * STEM_ROWW; idx += 256) {
+                const int r = idx / STEM_ROWW, c = idx - r * STEM_ROWW;
+                const int ci = r / STEM_IR, ir = r - ci * STEM_IR;
+                const int ih = 2 * oh0 + ir - 1, iw = iw0 + c;
+                const bool ok = ih >= 0 && ih < H && iw >= 0 && iw < W;
+                rows[r][3 + c] = ok ? img[(((long)n * 3 + ci) * H + ih) * (long)W + iw] : 0.f;
+            }
+        }
+        if (tl + gridDim.x < tiles) fetch(tl + gridDim.x);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {                       // wave w: the 32-pixel group w of both output rows
+            const int px0 = wave * 32;
+            const bool rowok = oh0 + j < OH;
+            frag fb[2];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float x = krow[nt] >= 0 ? rows[krow[nt] < 0 ? 0 : krow[nt] + 2 * j][2 * (px0 + 8 * g + e) + kcol[nt]] : 0.f;
+                    const T xr = from_f<T>(x);
+                    fb[nt][e] = xr;
+                    g3[nt] += (rowok && ow0 + px0 + 8 * g + e < OW) ? to_f<T>(xr) : 0.f;
+                }
+            }
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                const T* p = zs + (j * STEM_SEG + px0 + 8 * g + q4) * LDY + ct * 16 + c4;
+                const frag fz = stem_tr_frag<T>(p, p + 4 * LDY);
+                const frag fy = stem_tr_frag<T>(p + TILE, p + TILE + 4 * LDY);
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    acc1[ct][nt] = ops::mma(fz, fb[nt], acc1[ct][nt]);
+                    acc2[ct][nt] = ops::mma(fy, fb[nt], acc2[ct][nt]);
+                }
+            }
+        }
+    }
+    // the two tiles become: G1 | G2 [COUT][32], G3 [32] (laid out as the partial block), the channel-sum exchange [256][RED]
+    float* sum = reinterpret_cast<float*>(zs);
+    float* g3s = sum + 2 * COUT * 32;
+    float* red = g3s + 32;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {                         // the four 16-lane groups of a wave hold pixels 8g .. 8g+7 of a k
+        g3[nt] += __shfl_xor(g3[nt], 16, 64);
+        g3[nt] += __shfl_xor(g3[nt], 32, 64);
+    }
+    // D rows = co (ct*16 + g*4 + r), cols = k (nt*16 + i16)
+    // the four waves add their sums one after the other (fixed order: the result does not depend on the schedule)
+    for (int wv = 0; wv < 4; ++wv) {
+        __syncthreads();
+        if (wave == wv) {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float* e = &sum[(ct * 16 + g * 4 + r) * 32 + nt * 16 + i16];
+                        e[0] = wv == 0 ? acc1[ct][nt][r] : e[0] + acc1[ct][nt][r];
+                        e[COUT * 32] = wv == 0 ? acc2[ct][nt][r] : e[COUT * 32] + acc2[ct][nt][r];
+                    }
+            if (g == 0) {
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) g3s[nt * 16 + i16] = wv == 0 ? g3[nt] : g3s[nt * 16 + i16] + g3[nt];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { red[tid * RED + j] = s[j]; red[tid * RED + 8 + j] = q[j]; }
+    __syncthreads();
+    float* o = part + (long)blockIdx.x * stem_bn_block(COUT);
+    for (int c = tid; c < 2 * COUT * 32 + 32; c += 256) o[c] = sum[c];
+    // channel ch's two sums over the PPT threads that hold its chunk, in thread order
+    for (int t = tid; t < 2 * COUT; t += 256) {
+        const int which = t / COUT, ch = t - which * COUT, cl = ch >> 3, j = ch & 7;
+        float a = 0.f;
+        for (int rr = 0; rr < PPT; ++rr) a += red[(rr * CPP + cl) * RED + which * 8 + j];
+        o[2 * COUT * 32 + 32 + t] = a;
+    }
+}
+
+// One launch, one workgroup per output channel: lane k (32) x part (32) sums the workgroups' partial blocks in a fixed order
+// in double, derives dbeta, dgamma, A, B, D (bn_bwd_coef_d) and forms dW = A*G1 + B*G2 + D*G3 in double -- B*G2 + D*G3
+// cancel when |mean| / std is large, so the products are never rounded to fp32 before the sum.
+template <typename P>
+__global__ __launch_bounds__(1024) void k_stem_bn_wgrad_finalize(const float* __restrict__ part, int nslab, int Cout, float count,
+                                                                 const void* __restrict__ gamma_, const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd, void* __restrict__ dgamma_,
+                                                                 void* __restrict__ dbeta_, P* __restrict__ dw, int pdt) {
+    __shared__ double red[5][32][33];
+    const PIn gamma{gamma_, pdt}; const PIo dgamma{dgamma_, pdt}, dbeta{dbeta_, pdt};
+    const int co = blockIdx.x, k = threadIdx.x & 31, sub = threadIdx.x >> 5;
+    const long bs = stem_bn_block(Cout);
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+    for (int b = sub; b < nslab; b += 32) {
+        const float* p = part + b * bs;
+        a[0] += p[co * 32 + k];
+        a[1] += p[(Cout + co) * 32 + k];
+        a[2] += p[Cout * 64 + k];
+        a[3] += p[Cout * 64 + 32 + co];
+        a[4] += p[Cout * 64 + 32 + Cout + co];
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) red[i][sub][k] = a[i];
+    __syncthreads();
+    if (sub != 0) return;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        double t = 0.0;
+        for (int j = 0; j < 32; ++j) t += red[i][j][k];
+        a[i] = t;
+    }
+    const BnBwdCoefD c = bn_bwd_coef_d(a[3], a[4], count, gamma, mean, invstd, co);
+    if (k == 0) { dbeta.st(co, (float)c.dbeta); dgamma.st(co, (float)c.dgamma); }
+    if (k < 27) dw[co * 27 + k] = from_f<P>((float)(c.A * a[0] + c.B * a[1] + c.D * a[2]));
+}
+
+template <typename T, int ACT>
+int launch_stem_bn_wgrad(const float* img, const void* dout, int ldd, const void* y, int ldy, const float* scale,
+                         const float* shift, float* part, int N, int H, int W, int OH, int OW, int Cout, int* nslab, hipStream_t st) {
+    const long tiles = (long)N * ((OH + 1) / 2) * ((OW + STEM_SEG - 1) / STEM_SEG);
+    if (tiles <= 0) return YOLO_ERR_ARG;
+    const int grid = (int)(tiles < STEM_BN_SLABS ? tiles : STEM_BN_SLABS);
+    *nslab = grid;
+#define STEM_BW(CT) hipLaunchKernelGGL((k_stem_bn_wgrad<T, CT, ACT>), dim3(grid), dim3(256), 0, st, img, (const T*)dout, ldd, (const T*)y, ldy, scale, shift, part, N, H, W, OH, OW, tiles)
+    switch (Cout / 16) {
+        case 1: STEM_BW(1); break;
+        case 2: STEM_BW(2); break;
+        case 3: STEM_BW(3); break;
+        case 4: STEM_BW(4); break;
+        case 6: STEM_BW(6); break;
+        case 8: STEM_BW(8); break;
+        default: return YOLO_ERR_ARG;
+    }
+#undef STEM_BW
+    return YOLO_LAUNCH_CHECK();
+}
+
 template <typename T>
 int launch_stem_conv(const float* img, const void* wp, void* y, int ldy, float* stats, int N, int H, int W, int OH, int OW,
                      int Cout, const float* bias, int act, hipStream_t st) {
@@ -472,6 +740,39 @@ int yolo_stem_wgrad(const float* img, const void* dy, int ldy, float* partial, v
         case YOLO_F16:  hipLaunchKernelGGL((k_stem_wgrad_reduce<f16_t>), dim3(grid), dim3(256), 0, st, partial, nslab, Cout, (f16_t*)dw); break;
         default: return YOLO_ERR_DTYPE;
     }
+    return YOLO_LAUNCH_CHECK();
+}
+
+// fp32 elements of the scratch yolo_stem_bn_wgrad needs: one partial block per workgroup
+long yolo_stem_bn_wgrad_ws_elems(int Cout) { return STEM_BN_SLABS * stem_bn_block(Cout); }
+
+// The stem's BatchNorm + activation backward AND its weight gradient in one pass (training mode; same eligibility as
+// yolo_stem_conv_fwd): from the fp32 NCHW image, dout and the stored conv output y (both [N][OH][OW][ld >= Cout], dtype)
+// and the forward's scale / shift / mean / invstd -> dw OIHW (Cout,3,3,3) of dw_dtype, dgamma / dbeta [Cout] of pdt.
+// BatchNorm's input gradient is not formed.  No atomics: two launches of the same inputs give the same bits.
+int yolo_stem_bn_wgrad(const float* img, const void* dout, int ldd, const void* y, int ldy, const float* scale, const float* shift,
+                       const void* gamma, const float* mean, const float* invstd, float* partial, void* dw, int dw_dtype,
+                       void* dgamma, void* dbeta, int N, int H, int W, int OH, int OW, int Cout, int act, int dtype, int pdt,
+                       hipStream_t st) {
+    if (!yolo_stem_conv_eligible(YOLO_F32, dtype, Cout) || !pdt_ok(pdt) || (act != 0 && act != 1)) return YOLO_ERR_ARG;
+    if (ldd < Cout || (ldd & 7) || (reinterpret_cast<uintptr_t>(dout) & 15)) return YOLO_ERR_ARG;
+    if (ldy < Cout || (ldy & 7) || (reinterpret_cast<uintptr_t>(y) & 15)) return YOLO_ERR_ARG;
+    if (OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return YOLO_ERR_ARG;
+    int nslab = 0, rc;
+#define STEM_BW_ACT(T) (act ? launch_stem_bn_wgrad<T, 1>(img, dout, ldd, y, ldy, scale, shift, partial, N, H, W, OH, OW, Cout, &nslab, st) \
+                            : launch_stem_bn_wgrad<T, 0>(img, dout, ldd, y, ldy, scale, shift, partial, N, H, W, OH, OW, Cout, &nslab, st))
+    rc = dtype == YOLO_BF16 ? STEM_BW_ACT(bf16_t) : STEM_BW_ACT(f16_t);
+#undef STEM_BW_ACT
+    if (rc) return rc;
+    const float count = (float)((long)N * OH * OW);
+#define STEM_BW_FIN(P) hipLaunchKernelGGL((k_stem_bn_wgrad_finalize<P>), dim3(Cout), dim3(1024), 0, st, partial, nslab, Cout, count, gamma, mean, invstd, dgamma, dbeta, (P*)dw, pdt)
+    switch (dw_dtype) {
+        case YOLO_F32:  STEM_BW_FIN(float); break;
+        case YOLO_BF16: STEM_BW_FIN(bf16_t); break;
+        case YOLO_F16:  STEM_BW_FIN(f16_t); break;
+        default: return YOLO_ERR_DTYPE;
+    }
+#undef STEM_BW_FIN
     return YOLO_LAUNCH_CHECK();
 }
 

@@ -395,6 +395,19 @@ def _stem_grads(x, weight, dy, fused):
     return _param_grad(x.device, weight.shape, weight.dtype, (x, dy), run) if lazy else run()
 
 
+# The stem's training backward as one pass over (dout, y, image) -- ops.stem_bn_wgrad: BatchNorm's input gradient is never
+# formed -- instead of _bn_act_grads + _stem_grads (reduce, apply, weight gradient).  0: the three-launch path, for A/B runs.
+STEM_BWD_FUSED = os.environ.get("YOLO_STEM_BWD_FUSED", "1") == "1"
+
+
+def _stem_bn_grads(x, weight, dout, y, saved, act):
+    """(dw, dgamma, dbeta) of the fused stem in training mode.  Runs on the backward's own stream, deferred or not: it is the
+    last node of the main chain, the side queue is still draining the large-map weight gradients there, and it writes
+    dgamma / dbeta, which are plain autograd outputs.  Fixed-order sums: the deterministic mode takes it as it is."""
+    scale, shift, mean, invstd, gamma = saved
+    return ops.stem_bn_wgrad(x, dout, y, scale, shift, mean, invstd, gamma, act, weight.dtype)
+
+
 def _dw_grads(x, weight, dy, xshape, link, want_dx, want_dw):
     """(dx, dw) of a depthwise 3x3 conv; `link`: the fan link of its input alias, if any."""
     dx = dw = None
@@ -497,10 +510,14 @@ class ConvBnAct(torch.autograd.Function):
         x, weight, y = ctx.saved_tensors[:3]
         T = y.dtype
         dout = _as_nhwc(dout, T)
-        dy, dgamma, dbeta = _bn_act_grads(dout, y, ctx.saved_tensors[3:], act, training, ctx.acc_b)
         want_dx, want_dw = ctx.needs_input_grad[:2]
         link = ctx.res_link if not has_res else None
-        if stem:
+        one_pass = stem and ctx.stem_fused and training and want_dw and STEM_BWD_FUSED
+        if not one_pass:
+            dy, dgamma, dbeta = _bn_act_grads(dout, y, ctx.saved_tensors[3:], act, training, ctx.acc_b)
+        if one_pass:
+            dx, (dw, dgamma, dbeta) = None, _stem_bn_grads(x, weight, dout, y, ctx.saved_tensors[3:], act)
+        elif stem:
             dx, dw = None, (_stem_grads(x, weight, dy, ctx.stem_fused) if want_dw else None)
         elif depthwise:
             dx, dw = _dw_grads(x, weight, dy, xshape, link if (link is not None and link.fan) else None, want_dx, want_dw)

@@ -385,6 +385,24 @@ def stem_wgrad(img, dy, w_dtype, out=None):
     return dw
 
 
+def stem_bn_wgrad(img, dout, y, scale, shift, mean, invstd, gamma, act, w_dtype, out=None):
+    """The stem's training-mode backward in one pass over (dout, y, image): -> (dw, dgamma, dbeta).  dw[co] =
+    A G1[co] + B G2[co] + D G3 with (A, B, D) the constants of BatchNorm's input gradient A dz + B y + D and G1, G2, G3 the
+    pixel sums of dz X, y X and X (X: the unfolded image): that gradient is never formed.  Fixed-order partial sums, no
+    atomics: serves the default and the deterministic mode.  dgamma / dbeta come in gamma's dtype."""
+    n, _, h, w = img.shape
+    _, cout, oh, ow, ldy = geom(y)
+    ldd = geom(dout)[4]
+    dw = torch.empty((cout, 3, 3, 3), dtype=w_dtype, device=img.device) if out is None else out
+    assert dw.shape == (cout, 3, 3, 3) and dw.dtype == w_dtype and dw.is_contiguous() and img.is_contiguous()
+    assert tuple(dout.shape) == tuple(y.shape) and dout.dtype == y.dtype
+    part = torch.empty(lib.query("yolo_stem_bn_wgrad_ws_elems", cout), dtype=torch.float32, device=img.device)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+    lib.call("yolo_stem_bn_wgrad", _p(img), _p(dout), ldd, _p(y), ldy, _p(scale), _p(shift), _p(gamma), _p(mean), _p(invstd),
+             _p(part), _p(dw), dt(w_dtype), _p(dgamma), _p(dbeta), n, h, w, oh, ow, cout, int(act), dt(y), dt(gamma), _stream(img))
+    return dw, dgamma, dbeta
+
+
 def stem_pack_weights(w, dtype):
     """OIHW (Cout,3,3,3) -> forward-packed [Cout][32] matrix for conv_fwd(k=1) on the column tensor."""
     w = w if w.is_contiguous() else w.contiguous()

@@ -156,6 +156,12 @@ int yolo_stem_conv_fwd(const float* img, const void* wp, void* y, int ldy, float
    partial = fp32 scratch [yolo_stem_wgrad_slabs()][Cout][32]; dw = OIHW (Cout,3,3,3) of dw_dtype */
 int yolo_stem_wgrad_slabs();
 int yolo_stem_wgrad(const float* img, const void* dy, int ldy, float* partial, void* dw, int dw_dtype, int N, int H, int W, int OH, int OW, int Cout, int dtype, hipStream_t st);
+/* the stem's training-mode BatchNorm + activation backward and its weight gradient in one pass over (dout, y, image): the image
+   takes no gradient, so BatchNorm's input gradient A*dz + B*y + D is never formed -- dw = A*G1 + B*G2 + D*G3 from three pixel
+   sums.  partial = fp32 scratch of yolo_stem_bn_wgrad_ws_elems(Cout) elements; scale / shift / mean / invstd: the forward's;
+   dw = OIHW (Cout,3,3,3) of dw_dtype, dgamma / dbeta [Cout] of pdt (gamma's dtype); same eligibility as yolo_stem_conv_fwd */
+long yolo_stem_bn_wgrad_ws_elems(int Cout);
+int yolo_stem_bn_wgrad(const float* img, const void* dout, int ldd, const void* y, int ldy, const float* scale, const float* shift, const void* gamma, const float* mean, const float* invstd, float* partial, void* dw, int dw_dtype, void* dgamma, void* dbeta, int N, int H, int W, int OH, int OW, int Cout, int act, int dtype, int pdt, hipStream_t st);
 /* depthwise 3x3 (groups == channels: model_blocks.py:183, head.py:56,58) */
 int yolo_dwconv3x3_fwd(const void* x, int ldx, const float* w, void* y, int ldy, int N, int H, int W, int C, int dtype, hipStream_t st);
 int yolo_dwconv3x3_fwd_stats(const void* x, int ldx, const float* w, void* y, int ldy, float* stats, int N, int H, int W, int C, int dtype, hipStream_t st);
