@@ -34,8 +34,12 @@ __global__ void k_conv_generic(ConvGeom g, const T* __restrict__ src, const T* _
                 for (int j = 0; j < V; ++j) acc = fmaf(xs[j], wv[j], acc);
             }
         }
-        long dp = ((n * g.Hd + a * g.ostep + g.ooff_h) * g.Wd + b * g.ostep + g.ooff_w) * (long)g.ldd + cd;
-        if (ACC) acc += to_f<T>(dst[dp]);
+        long pix = (n * g.Hd + a * g.ostep + g.ooff_h) * g.Wd + b * g.ostep + g.ooff_w;
+        long dp = pix * (long)g.ldd + cd;
+        if (ACC) {                        // both accumulate sources in fp32, ONE rounding (as the MFMA epilogues: conv_dev.h)
+            acc += to_f<T>(dst[dp]);
+            if (g.acc2 != nullptr) acc += to_f<T>(((const T*)g.acc2)[pix * (long)g.ld2 + cd]);
+        }
         dst[dp] = from_f<T>(acc);
     }
 }
@@ -261,12 +265,15 @@ int grid_for(long total) {
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
+// *took_acc2: the kernel that ran added g.acc2 in its own epilogue (k_conv_generic does, the LDS-tiled fp32 kernel does not)
 int launch_generic(const ConvGeom& g, const void* src, const void* wm, const float* bias, void* dst, int accumulate,
-                   int dtype, hipStream_t st) {
+                   int dtype, hipStream_t st, bool* took_acc2) {
     long total = (long)g.N * g.Hg * g.Wg * g.Cd;
+    *took_acc2 = false;
     if (total == 0) return YOLO_OK;
     if (dtype == YOLO_F32 && f32_conv_eligible(g, src, wm, dst))        // LDS-tiled fp32 kernel (conv_f32.hip)
         return f32_conv_launch(g, (const float*)src, (const float*)wm, bias, (float*)dst, accumulate, st);
+    *took_acc2 = accumulate != 0;
     YOLO_DISPATCH_T(dtype, {
         bool ok = vecok<T>(src, g.lds, g.Cs) && vecok<T>(wm, g.Kpad, g.Cs);
         if (ok) {
@@ -290,8 +297,11 @@ int launch_generic(const ConvGeom& g, const void* src, const void* wm, const flo
 // the VALU / fp32 kernels with what only the MFMA epilogues have (second accumulate source, statistics) as extra passes
 int valu_conv_launch(const ConvGeom& g, const void* src, const void* wm, const float* bias, void* dst, int accumulate, int dtype,
                      hipStream_t st) {
-    int rc = launch_generic(g, src, wm, bias, dst, accumulate, dtype, st);
-    if (rc == YOLO_OK && accumulate && g.acc2 != nullptr)      // the generic kernels have one accumulate source: add the second
+    bool took_acc2 = false;
+    int rc = launch_generic(g, src, wm, bias, dst, accumulate, dtype, st, &took_acc2);
+    // the generic kernel adds the second accumulate source in fp32 before its one rounding; the LDS-tiled fp32 kernel has one
+    // source only: there the second is an extra pass (a second rounding, of fp32)
+    if (rc == YOLO_OK && accumulate && g.acc2 != nullptr && !took_acc2)
         rc = yolo_copy_channels(g.acc2, g.ld2, dst, g.ldd, (long)g.N * g.Hd * g.Wd, g.Cd, 1, dtype, st);
     if (rc == YOLO_OK && g.stats)         // the generic kernel has no statistics epilogue: one extra pass over y
         rc = yolo_bn_stats_acc(dst, g.ldd, (long)g.N * g.Hd * g.Wd, g.Cd, dtype, g.stats, st);

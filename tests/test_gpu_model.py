@@ -198,7 +198,9 @@ def test_all_gradients_within_band_of_fp32_oracle(preset, res, precision):
     ~1e-1 max-rel), so the yardstick is the oracle itself run under CPU bf16 autocast -- the reference's own bf16 path
     -- against the same fp32 result: per tensor the HIP error may not exceed 2x the CPU-bf16 error + 0.05, and the
     median over all tensors may not exceed 1.25x the CPU-bf16 median.  Preset l = BASELINE config 4's model (C3K inside
-    every C3K2, two blocks per stage)."""
+    every C3K2, two blocks per stage).
+    This band is the end-to-end anchor, not the tight check: a launch wrong by a few percent of one gradient's norm passes
+    it.  tests/test_gpu_launch_replay.py holds every launch of the 16-bit path to its leaf's own derived bound."""
     cfg = ob.PRESETS[preset]
     model = _model(seed=2, cfg=cfg).train()
     img = torch.randn(2, 3, res, res, generator=torch.Generator().manual_seed(9))

@@ -41,11 +41,26 @@ def _scalar(v):
     return v if v is None or isinstance(v, (bool, int, float, str)) else str(v)
 
 
+class Owners:
+    """Which record returned the storage behind a tensor (shared with tests/launch_replay.py)."""
+
+    def __init__(self):
+        self._owner = {}        # storage address -> (ordinal of the last record that returned it, the storage: kept
+        #                         alive so that no later allocation can take its address)
+
+    def of(self, t):
+        return self._owner.get(t.untyped_storage().data_ptr(), (-1, None))[0]
+
+    def returned(self, ordinal, result):
+        for t in _tensors(result):
+            st = t.untyped_storage()
+            self._owner[st.data_ptr()] = (ordinal, st)
+
+
 class Tracer:
     def __init__(self):
         self.records = []
-        self._owner = {}        # storage address -> (ordinal of the last record that returned it, the storage: kept
-        #                         alive so that no later allocation can take its address)
+        self.owners = Owners()
 
     def _record(self, name, sig, args, kwargs):
         bound = sig.bind(*args, **kwargs)
@@ -59,8 +74,7 @@ class Tracer:
                 rec["scalars"][arg] = _scalar(v)
             if arg in LINK_ARGS and v is not None:
                 if isinstance(v, torch.Tensor):
-                    src = self._owner.get(v.untyped_storage().data_ptr(), (-1, None))[0]
-                    rec["links"][arg] = [src, v.storage_offset()]
+                    rec["links"][arg] = [self.owners.of(v), v.storage_offset()]
                 else:
                     rec["links"][arg] = _scalar(v)
         return rec
@@ -73,9 +87,7 @@ class Tracer:
             ordinal = len(self.records)
             self.records.append(rec)
             result = fn(*args, **kwargs)
-            for t in _tensors(result):
-                st = t.untyped_storage()
-                self._owner[st.data_ptr()] = (ordinal, st)
+            self.owners.returned(ordinal, result)
             return result
         return traced
 
