@@ -366,7 +366,7 @@ int yolo_conv_unpack_wgrad(const float* dwp, int O, int I, int k, void* dw_oihw,
 }
 
 long yolo_conv2d_wgrad_plan(int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype) {
-    if (!conv_supported(k, stride)) return -1;
+    if (!conv_supported(k, stride, Cin, Cout)) return -1;
     static const long long dummy[2] = {0, 0};
     if (!mfma_wgrad_eligible(Cin, Cout, Cin, Cout, dtype, dummy, dummy)) return 0;
     return mfma_wgrad2_plan(round_up32(k * k * Cin), N, H, W, Cin, OH, OW, Cout, k);
@@ -386,7 +386,7 @@ static int wgrad_path(const void* x, int ldx, const void* dy, int ldy, int N, in
 // fp32 scratch elements yolo_conv2d_wgrad needs for these arguments
 long yolo_conv2d_wgrad_ws_elems(const void* x, int ldx, const void* dy, int ldy, int N, int H, int W, int Cin, int OH,
                                 int OW, int Cout, int k, int stride, int dtype, int algo) {
-    if (!conv_supported(k, stride)) return 0;
+    if (!conv_supported(k, stride, Cin, Cout)) return 0;
     const int Kpad = round_up32(k * k * Cin);
     if (wgrad_path(x, ldx, dy, ldy, N, H, W, Cin, OH, OW, Cout, dtype, algo) == 2)
         return mfma_wgrad2_ws_elems(Kpad, N, H, W, Cin, OH, OW, Cout, k);
@@ -398,7 +398,7 @@ long yolo_conv2d_wgrad_ws_elems(const void* x, int ldx, const void* dy, int ldy,
 int yolo_conv2d_wgrad(const void* x, int ldx, const void* dy, int ldy, float* ws, void* dw_oihw, int dw_dtype, int N,
                       int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, int algo,
                       hipStream_t st) {
-    if (!conv_supported(k, stride)) return YOLO_ERR_ARG;
+    if (!conv_supported(k, stride, Cin, Cout)) return YOLO_ERR_ARG;
     const int K = k * k * Cin, Kpad = round_up32(K);
     const int path = wgrad_path(x, ldx, dy, ldy, N, H, W, Cin, OH, OW, Cout, dtype, algo);
     if (path == 2)
@@ -491,10 +491,11 @@ int yolo_dwconv3x3_dgrad(const void* dy, int lddy, const float* w, void* dx, int
 
 // number of row slabs (= partial blocks) yolo_dwconv3x3_wgrad uses for an (N, H) map
 int yolo_dw_wgrad_nslab(int N, int H) {
-    int nrows = N * H;
-    int slabs = nrows < 1024 ? nrows : 1024;
-    int rps = (nrows + slabs - 1) / slabs;
-    return (nrows + rps - 1) / rps;
+    const long nrows = (long)N * H;                          // N * H may pass 2^31: the slab count never does
+    if (nrows < 1) return 0;
+    const long slabs = nrows < 1024 ? nrows : 1024;
+    const long rps = (nrows + slabs - 1) / slabs;
+    return (int)((nrows + rps - 1) / rps);
 }
 
 // dw fp32 [C][9]; partial: fp32 scratch [nslab][C][9]

@@ -100,3 +100,8 @@ extern "C" int yolo_copy_channels(const void* src, int ld_src, void* dst, int ld
                                   hipStream_t st);
 
 static inline bool conv_supported(int k, int stride) { return (k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)); }
+// K = k * k * channels and its padding to 32 are `int` (ConvGeom, the packed weight rows): a problem whose packed row would
+// not fit one is refused like an unsupported kernel size, before any such product is formed
+static inline bool conv_supported(int k, int stride, int Cin, int Cout) {
+    return conv_supported(k, stride) && Cin >= 0 && Cout >= 0 && (long)k * k * (Cin > Cout ? Cin : Cout) <= 2147483647L - 31;
+}

@@ -243,7 +243,7 @@ ConvGeom dgrad_geom(int lddy, int lddx, int N, int H, int W, int Cin, int OH, in
 int conv2d_dgrad_impl(const void* dy, int lddy, const void* wb, void* dx, int lddx, const void* acc2, int ld2, int N, int H,
                       int W, int Cin, int OH, int OW, int Cout, int k, int stride, int accumulate, int dtype, int algo,
                       hipStream_t st) {
-    if (!conv_supported(k, stride)) return YOLO_ERR_ARG;
+    if (!conv_supported(k, stride, Cin, Cout)) return YOLO_ERR_ARG;
     size_t esz = dtype == YOLO_F32 ? 4 : 2;
     int ncls = stride == 2 ? 4 : 1;
     ConvGeom gs[4];
@@ -278,7 +278,7 @@ extern "C" {
 int yolo_conv2d_fwd(const void* x, int ldx, const void* wp, const float* bias, void* y, int ldy, float* stats_acc, int N,
                     int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int dtype, int algo,
                     hipStream_t st) {
-    if (!conv_supported(k, stride) || (stats_acc && bias)) return YOLO_ERR_ARG;
+    if (!conv_supported(k, stride, Cin, Cout) || (stats_acc && bias)) return YOLO_ERR_ARG;
     int pad = k / 2;
     if (OH != (H + 2 * pad - k) / stride + 1 || OW != (W + 2 * pad - k) / stride + 1) return YOLO_ERR_ARG;
     ConvGeom g = fwd_geom(ldx, ldy, stats_acc, N, H, W, Cin, OH, OW, Cout, k, stride);
@@ -292,7 +292,7 @@ int yolo_conv2d_fwd(const void* x, int ldx, const void* wp, const float* bias, v
 int yolo_conv2d_fwd_act(const void* x, int ldx, const void* wp, const float* bias, const void* res, int ldr, void* y, int ldy,
                         int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int act, int dtype,
                         hipStream_t st) {
-    if (!conv_supported(k, stride) || (act != 0 && act != 1)) return YOLO_ERR_ARG;
+    if (!conv_supported(k, stride, Cin, Cout) || (act != 0 && act != 1)) return YOLO_ERR_ARG;
     int pad = k / 2;
     if (OH != (H + 2 * pad - k) / stride + 1 || OW != (W + 2 * pad - k) / stride + 1) return YOLO_ERR_ARG;
     if (res != nullptr && ((ldr & 3) || (reinterpret_cast<uintptr_t>(res) & 7))) return 1;
@@ -321,7 +321,7 @@ int yolo_conv2d_dgrad_acc2(const void* dy, int lddy, const void* wb, void* dx, i
 // Which kernel a forward / data-gradient launch takes (tests assert that their shapes reach the variant they mean to cover):
 // conv_select's answer for dense rows and aligned pointers, as kind * 1000 + width (include/yolo_hip.h)
 int yolo_conv2d_plan(int N, int H, int W, int Cin, int OH, int OW, int Cout, int k, int stride, int mode, int cls, int dtype) {
-    if (!conv_supported(k, stride)) return -1;
+    if (!conv_supported(k, stride, Cin, Cout)) return -1;
     ConvGeom gs[4];
     const int n = (mode == 1 && stride == 2) ? 4 : 1;
     if (n == 4 && (cls < 0 || cls > 3)) return -1;

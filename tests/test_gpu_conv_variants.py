@@ -445,7 +445,8 @@ def test_wgrad_1x1_every_tile(to, ti, pf):
 @pytest.mark.parametrize("cin,cout,k,s", [(72, 88, 3, 1), (72, 88, 3, 2), (136, 120, 1, 1)])
 def test_wgrad_first_mfma_design_with_atomics(cin, cout, k, s, monkeypatch):
     """algo 3 (conv_generic.hip: wgrad_path): the first MFMA weight-gradient design, float atomics into one matrix -- the
-    automatic route for tensors of 2^30 elements and more, which no test reaches by size.  Held to the same bound; no
+    automatic route for tensors of 2^30 elements and more (reached by size, by the launcher's own choice, in
+    tests/test_gpu_addressing.py; here it is forced on small maps with partial tiles).  Held to the same bound; no
     bit-equality of two launches (atomics)."""
     monkeypatch.setattr(ops(), "ALGO", 3)
     assert lib().query("yolo_conv2d_wgrad_plan", 3, 37, 41, cin, *ops().conv_out_hw(37, 41, k, s), cout, k, s, lib().BF16) > 0   # MFMA-eligible: algo 3 takes the first design
