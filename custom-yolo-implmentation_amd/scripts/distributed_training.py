@@ -155,7 +155,10 @@ def main(args):
               log_interval=tr_cfg.get("log_interval", 10), checkpoint_dir=ckpt_dir,
               iou_threshold=tr_cfg.get("iou_threshold", 0.5), conf_threshold=tr_cfg.get("conf_threshold", 0.25),
               distributed_mode=args.mode, precision=args.precision, captured_step=captured,
-              grad_compress=(tr_cfg.get("ddp") or {}).get("grad_compress"), max_grad_norm=max_grad_norm, ema=ema)
+              grad_compress=(tr_cfg.get("ddp") or {}).get("grad_compress"), max_grad_norm=max_grad_norm, ema=ema,
+              # optional key `training.val_ap: {conf, nms_iou, max_det}`: validation additionally computes COCO's mAP50 and
+              # mAP50-95 on the device (NMS + COCOeval's matching and precision table; absent = off; the reference has none)
+              val_ap=tr_cfg.get("val_ap", None))
     finally:
         if run is not None:
             import wandb

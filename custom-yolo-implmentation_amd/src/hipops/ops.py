@@ -894,3 +894,33 @@ def val_match(rows, count, gt, gt_off, iou_threshold, nc, skip_empty_gt, counter
     assert counters.dtype == torch.int64 and counters.numel() == 5 + 4 * nc
     lib.call("yolo_val_match", _p(rows), _p(count), n, k, _p(gt), _p(gt_off), float(iou_threshold), nc, int(skip_empty_gt),
              _p(counters), _p(status), _stream(rows))
+
+
+def ap_match(det, count, gt, gt_off, iou_thr, nc, gt_count, status):
+    """COCOeval's per-image matching for a batch of `nms` rows: det fp32 [N][K][6] (x1, y1, x2, y2, score, cls; descending
+    score), count int32 [N], gt fp32 [total][5] (cx, cy, w, h, cls), gt_off int32 [N+1], iou_thr float64 [1..10] on the
+    device; accumulates into gt_count int64 [nc] and status int32 [1].
+    -> (key int64 [N][K], tp int32 [N][K] holding the uint32 bit sets: bit t = matched at iou_thr[t])."""
+    n, k, six = det.shape
+    assert six == 6 and det.dtype == torch.float32 and det.is_contiguous()
+    assert gt.dtype == torch.float32 and gt.is_contiguous() and gt_off.dtype == torch.int32 and count.dtype == torch.int32
+    assert gt_off.numel() == n + 1 and count.numel() == n
+    assert iou_thr.dtype == torch.float64 and iou_thr.is_contiguous() and iou_thr.device == det.device
+    assert gt_count.dtype == torch.int64 and gt_count.numel() == nc and status.dtype == torch.int32
+    key = torch.empty((n, k), dtype=torch.int64, device=det.device)
+    tp = torch.empty((n, k), dtype=torch.int32, device=det.device)
+    lib.call("yolo_ap_match", _p(det), _p(count), n, k, _p(gt), _p(gt_off), _p(iou_thr), iou_thr.numel(), nc, _p(key), _p(tp),
+             _p(gt_count), _p(status), _stream(det))
+    return key, tp
+
+
+def ap_curve(key, tp, gt_count, rec_thr, nc, n_thr):
+    """COCOeval's precision[T, R, K] for area "all": key int64 [D] / tp int32 [D] sorted ascending by key with a stable sort,
+    gt_count int64 [nc], rec_thr float64 [101] on the device -> precision float64 [nc][n_thr][101] (-1: class without targets)."""
+    assert key.dtype == torch.int64 and tp.dtype == torch.int32 and key.dim() == 1 and key.shape == tp.shape
+    assert key.is_contiguous() and tp.is_contiguous()
+    assert gt_count.dtype == torch.int64 and gt_count.numel() == nc
+    assert rec_thr.dtype == torch.float64 and rec_thr.numel() == 101 and rec_thr.is_contiguous()
+    out = torch.empty((nc, n_thr, 101), dtype=torch.float64, device=gt_count.device)
+    lib.call("yolo_ap_curve", _p(key), _p(tp), key.numel(), _p(gt_count), _p(rec_thr), nc, n_thr, _p(out), _stream(gt_count))
+    return out

@@ -7,6 +7,8 @@ batch (one wave per image, `yolo_val_match`) and the counters stay in device mem
 `get_class_metrics()` / `sync()` fetch them with one copy.  `update()` keeps the reference's per-image signature;
 `update_batch()` takes the packed output of `decode_predictions_packed` (src/training/train_model.py).
 There is no host implementation: the tensors must live on the GPU like every other op of this package.
+`DetectionAP` (no reference counterpart) adds COCO's average precision the same way: matching per batch on the device
+(`yolo_ap_match`), the precision table once per evaluation (`yolo_ap_curve`), one copy.
 """
 from typing import Dict, List
 
@@ -123,6 +125,81 @@ class DetectionMetrics:
         return {"precision": float(p), "recall": float(r), "f1_score": float(np.float32(2) * (p * r) / (p + r + eps)),
                 "true_positives": int(tp), "false_positives": int(fp), "false_negatives": int(fn),
                 "ground_truths": int(self.class_gt_count[class_id])}
+
+
+class DetectionAP:
+    """COCO average precision on the device (no reference counterpart: the reference's `"mAP"` above is a
+    precision at one threshold and one confidence cut).  `update_batch` runs COCOeval's per-image matching at every IoU
+    threshold in one launch (`yolo_ap_match`) and keeps the batch's records on the device; `compute` sorts them (class
+    ascending, score descending, stable), builds COCOeval's precision[T, R, K] table for area "all" in one launch
+    (`yolo_ap_curve`) and fetches it with one copy.  The means over the table are host work, as COCOeval._summarize."""
+
+    def __init__(self, num_classes: int, iou_thresholds=np.linspace(0.5, 0.95, 10)):
+        self.num_classes = int(num_classes)
+        self.iou_thresholds = np.ascontiguousarray(iou_thresholds, dtype=np.float64).reshape(-1)
+        if not 1 <= self.iou_thresholds.size <= 10:
+            raise ValueError("DetectionAP: between 1 and 10 IoU thresholds expected")
+        at50 = np.flatnonzero(self.iou_thresholds == 0.5)
+        if at50.size == 0:
+            raise ValueError("DetectionAP: the IoU thresholds must contain 0.5 (mAP50 is read at it)")
+        self._at50 = int(at50[0])
+        self.rec_thresholds = np.linspace(0.0, 1.0, 101)
+        self.reset()
+
+    def reset(self):
+        self._records = []          # (key int64 [N][K], tp int32 [N][K]) per batch, on the device
+        self._dev = None            # (gt_count int64 [nc], status int32 [1], iou_thr float64, rec_thr float64 [101])
+
+    def _state(self, device):
+        if self._dev is None:
+            self._dev = (ops.zero_(torch.empty(self.num_classes, dtype=torch.int64, device=device)),
+                         ops.zero_(torch.empty(1, dtype=torch.int32, device=device)),
+                         torch.from_numpy(self.iou_thresholds).to(device), torch.from_numpy(self.rec_thresholds).to(device))
+        elif self._dev[0].device != device:
+            raise RuntimeError("DetectionAP: updates must stay on one device between reset() calls")
+        return self._dev
+
+    def update_batch(self, rows: torch.Tensor, count: torch.Tensor, targets: List[torch.Tensor]):
+        """rows fp32 [N][K][6] (x1, y1, x2, y2, score, cls: `ops.nms`), count int32 [N], targets: N tensors (Mi, 5) of
+        [cx, cy, w, h, class].  Images without targets count: their rows are false positives.  Never reads the device."""
+        dev = rows.device
+        gt_count, status, iou_thr, _ = self._state(dev)
+        sizes = [int(t.shape[0]) if t.numel() else 0 for t in targets]
+        if len(sizes) != rows.shape[0]:
+            raise ValueError("one target tensor per image expected")
+        parts = [t.reshape(-1, 5).to(device=dev, dtype=torch.float32) for t, s in zip(targets, sizes) if s]
+        gt = torch.cat(parts) if parts else torch.zeros(1, 5, dtype=torch.float32, device=dev)
+        off = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32).to(dev, non_blocking=True)
+        self._records.append(ops.ap_match(rows.contiguous(), count, gt.contiguous(), off, iou_thr, self.num_classes,
+                                          gt_count, status))
+
+    def compute(self) -> Dict[str, object]:
+        """-> {"mAP50", "mAP50-95": means over the table's entries > -1 (0.0 when no class has targets), "ap_per_class":
+        float64 [nc] (-1 for a class without targets), "precision": float64 [nc][n_thr][101]}."""
+        nc, nt = self.num_classes, self.iou_thresholds.size
+        if self._dev is None:
+            table = np.full((nc, nt, 101), -1.0)
+        else:
+            gt_count, status, _, rec_thr = self._dev
+            if self._records:
+                key, order = torch.sort(torch.cat([k.reshape(-1) for k, _ in self._records]), stable=True)
+                tp = torch.cat([t.reshape(-1) for _, t in self._records])[order].contiguous()
+            else:
+                key = torch.empty(0, dtype=torch.int64, device=gt_count.device)
+                tp = torch.empty(0, dtype=torch.int32, device=gt_count.device)
+            dev_table = ops.ap_curve(key, tp, gt_count, rec_thr, nc, nt)
+            host = torch.cat([dev_table.reshape(-1), status.double()]).cpu().numpy()         # the one copy
+            if host[-1] != 0:
+                raise RuntimeError("DetectionAP: an image had more than 1024 targets (yolo_ap_match limit)")
+            table = host[:-1].reshape(nc, nt, 101).copy()
+        per_class = np.full(nc, -1.0)
+        for c in range(nc):
+            if (table[c] > -1).any():
+                per_class[c] = float(np.mean(table[c][table[c] > -1]))
+
+        def mean(s):
+            return float(np.mean(s[s > -1])) if (s > -1).any() else 0.0
+        return {"mAP50": mean(table[:, self._at50]), "mAP50-95": mean(table), "ap_per_class": per_class, "precision": table}
 
 
 def compute_average_iou(predictions: List[torch.Tensor], targets: List[torch.Tensor]) -> float:

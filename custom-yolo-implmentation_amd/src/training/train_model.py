@@ -17,17 +17,48 @@ except ImportError:  # pragma: no cover
 
 from src.hipops import ops
 from src.training.distributed_setup import reduce_values
-from src.training.metrics import DetectionMetrics
+from src.training.metrics import DetectionAP, DetectionMetrics
 from src.training.utils_train import _is_sharded, checkpoint_states, save_checkpoint
 
 
-def decode_predictions_packed(preds, anchors, strides, conf_threshold=0.25, top_k=100):
+def decode_predictions_packed(preds, anchors, strides, conf_threshold=0.25, top_k=100, decoded=None):
     """Raw head output -> (rows fp32 [N][top_k][6] = cx, cy, w, h, class, score, zero padded; counts int32 [N]), all
     on the device: DFL expectation -> xywh * stride (yolo_head_decode), sigmoid best class, `>= conf`, top-k by score
-    (yolo_val_select); no NMS, no per-image launches, no host sync.  Reference :14-142."""
+    (yolo_val_select); no NMS, no per-image launches, no host sync.  Reference :14-142.
+    `decoded`: the output of `ops.head_decode` for these predictions, if the caller already has it."""
     nc = preds.shape[1] - 64
-    y = ops.head_decode(preds, anchors, strides, nc)            # (N, 4+nc, M): boxes + raw class logits
+    y = ops.head_decode(preds, anchors, strides, nc) if decoded is None else decoded    # (N, 4+nc, M): boxes + raw class logits
     return ops.val_select(y, nc, conf_threshold, top_k)
+
+
+_VAL_AP_KEYS = {"conf": 0.001, "nms_iou": 0.7, "max_det": 300}
+
+
+def val_ap_settings(val_ap):
+    """The optional `training.val_ap: {conf, nms_iou, max_det}` with its defaults filled in; None = off.  Unknown keys and
+    values outside their range raise."""
+    if val_ap is None:
+        return None
+    if not isinstance(val_ap, dict):
+        raise ValueError(f"training.val_ap must be a mapping with some of {sorted(_VAL_AP_KEYS)}")
+    unknown = sorted(set(val_ap) - set(_VAL_AP_KEYS))
+    if unknown:
+        raise ValueError(f"training.val_ap: unknown keys {unknown}; expected some of {sorted(_VAL_AP_KEYS)}")
+    cfg = {**_VAL_AP_KEYS, **val_ap}
+    cfg["conf"], cfg["nms_iou"], cfg["max_det"] = float(cfg["conf"]), float(cfg["nms_iou"]), int(cfg["max_det"])
+    if not 0.0 < cfg["conf"] < 1.0 or not 0.0 <= cfg["nms_iou"] <= 1.0 or cfg["max_det"] < 1:
+        raise ValueError(f"training.val_ap: expected 0 < conf < 1, 0 <= nms_iou <= 1, max_det >= 1, got {val_ap}")
+    return cfg
+
+
+def ap_update(ap, cfg, decoded, num_classes, gt_box):
+    """One validation batch of the COCO average precision: class-aware NMS (one class per anchor, so the candidate capacity
+    cannot overflow) on the decoded head output, then COCOeval's matching.  The head's class rows are logits and the NMS
+    compares them raw, so the confidence cut is the logit of `conf`; the scores stay logits, only their order matters."""
+    import math
+    rows, count, _ = ops.nms(decoded, num_classes, math.log(cfg["conf"] / (1.0 - cfg["conf"])), cfg["nms_iou"], None, False,
+                             False, cfg["max_det"])
+    ap.update_batch(rows, count, gt_box)
 
 
 def decode_predictions(preds, anchors, strides, conf_threshold=0.25, top_k=100, num_classes=171):
@@ -189,7 +220,7 @@ class ShardedTraining(CapturedTraining):
 
 
 def _run_epoch(model, loader, criterion, device, autocast_kw, rank, desc, optimizer=None, scaler=None, metrics=None,
-               conf_threshold=0.25, num_classes=171, on_step=None, captured=None):
+               conf_threshold=0.25, num_classes=171, on_step=None, captured=None, ap=None, val_ap=None):
     sums = [0.0, 0.0, 0.0]
     dev_sums = [None]
     if device != "cpu" and torch.cuda.is_available():
@@ -238,8 +269,11 @@ def _run_epoch(model, loader, criterion, device, autocast_kw, rank, desc, optimi
                 optimizer.step()
         elif metrics is not None:
             # one select + one matching launch per batch; images without ground truth are skipped (reference :326-328)
-            rows, count = decode_predictions_packed(preds, anchors, strides, conf_threshold=conf_threshold)
+            decoded = ops.head_decode(preds, anchors, strides, preds.shape[1] - 64) if ap is not None else None
+            rows, count = decode_predictions_packed(preds, anchors, strides, conf_threshold=conf_threshold, decoded=decoded)
             metrics.update_batch(rows, count, gt_box, skip_empty_targets=True)
+            if ap is not None:      # training.val_ap: the same decoded tensor through NMS and COCO's matching, one more pair of launches
+                ap_update(ap, val_ap, decoded, preds.shape[1] - 64, gt_box)
         account(i, loss_dict)
     if dev_sums[0] is not None:
         sums = [a + b for a, b in zip(sums, dev_sums[0].tolist())]
@@ -250,7 +284,7 @@ def _run_epoch(model, loader, criterion, device, autocast_kw, rank, desc, optimi
 def train(model, train_loader, val_loader, optimizer, scheduler, criterion, initial_epoch, num_epochs, device,
           num_classes=171, rank=0, use_wandb=False, wandb_instance=None, log_interval=10,
           checkpoint_dir="experiments/checkpoints", iou_threshold=0.5, conf_threshold=0.25, distributed_mode="ddp",
-          precision="float32", captured_step=None, grad_compress=None, max_grad_norm=None, ema=None):
+          precision="float32", captured_step=None, grad_compress=None, max_grad_norm=None, ema=None, val_ap=None):
     """`captured_step`: None (default) = the captured step where it applies AND has been verified on hardware (ddp mode on
     one GPU, plain parameters, capturable optimizer), True = also with more than one rank, False = the reference's eager
     loop.  `grad_compress`: None = fp32 gradient exchange (the reference's), "bf16" = bf16 buckets in the captured step.
@@ -258,7 +292,12 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
     HipAdamW.step); here it only refuses the routes that cannot clip and enables the train/grad_norm log.
     `ema`: a `ModelEMA` (config key training.ema) or None.  The average itself is kept inside the optimizer step; here the
     validation epoch -- loss, metrics and so the ReduceLROnPlateau schedule -- runs on the averaged weights
-    (`ema.applied(model)`), training continues on the raw ones, and the routes without an EMA are refused."""
+    (`ema.applied(model)`), training continues on the raw ones, and the routes without an EMA are refused.
+    `val_ap`: None, or the config's optional training.val_ap `{conf: 0.001, nms_iou: 0.7, max_det: 300}`: validation
+    additionally runs NMS and COCO's average precision on the device; the epoch summary, wandb and the returned
+    dict gain `mAP50` and `mAP50-95`.  Each rank evaluates its own shard, like the counters.
+    Returns the metric dict of the last validation epoch (None if no epoch ran)."""
+    val_ap = val_ap_settings(val_ap)
     if ema is not None:
         if distributed_mode in ("fsdp", "fsdp2") or getattr(model, "_native_shard", None) is not None:
             raise ValueError(f"training.ema is not supported in {distributed_mode} mode: the shadows of sharded parameters "
@@ -296,6 +335,8 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
                        dtype=torch.bfloat16 if precision == "bfloat16" else torch.float16,
                        enabled=(distributed_mode == "ddp" and use_amp))       # FSDP modes rely on their MP policy
     metrics = DetectionMetrics(num_classes=num_classes, iou_threshold=iou_threshold)
+    ap = DetectionAP(num_classes=num_classes) if val_ap is not None else None
+    md = None
 
     for epoch in range(initial_epoch, num_epochs):
         if hasattr(train_loader.sampler, "set_epoch"):
@@ -326,19 +367,25 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
 
         model.eval()
         metrics.reset()
+        if ap is not None:
+            ap.reset()
         with torch.no_grad(), (ema.applied(model) if ema is not None else contextlib.nullcontext()):
             va = _run_epoch(model, val_loader, criterion, device, autocast_kw, rank,
                             f"[Epoch {epoch + 1}/{num_epochs}] Validation", metrics=metrics,
-                            conf_threshold=conf_threshold, num_classes=num_classes)
+                            conf_threshold=conf_threshold, num_classes=num_classes, ap=ap, val_ap=val_ap)
         va = reduce_values(va, average=True)
         md = metrics.compute()
+        if ap is not None:
+            apd = ap.compute()
+            md["mAP50"], md["mAP50-95"] = apd["mAP50"], apd["mAP50-95"]
         scheduler.step(va[0])
 
         # a sharded model's full state is gathered by a collective: every rank takes part, rank 0 writes
         states = checkpoint_states(model, optimizer) if _is_sharded(model) else None
         if rank == 0:
             if use_wandb and wandb_instance:
-                wandb_instance.log({"epoch": epoch + 1, "train/epoch_loss": tr[0], "train/epoch_box_loss": tr[1],
+                extra = {"val/mAP50": md["mAP50"], "val/mAP50-95": md["mAP50-95"]} if ap is not None else {}
+                wandb_instance.log({**extra, "epoch": epoch + 1, "train/epoch_loss": tr[0], "train/epoch_box_loss": tr[1],
                                     "train/epoch_cls_loss": tr[2], "val/epoch_loss": va[0], "val/epoch_box_loss": va[1],
                                     "val/epoch_cls_loss": va[2], "val/precision": md["precision"],
                                     "val/recall": md["recall"], "val/f1_score": md["f1_score"], "val/mAP": md["mAP"],
@@ -350,6 +397,9 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, init
             w(f"  Train - Total: {tr[0]:.4f} | Box: {tr[1]:.4f} | Cls: {tr[2]:.4f}")
             w(f"  Val   - Total: {va[0]:.4f} | Box: {va[1]:.4f} | Cls: {va[2]:.4f}")
             w(f"  Metrics - Precision: {md['precision']:.4f} | Recall: {md['recall']:.4f} | F1: {md['f1_score']:.4f} | mAP: {md['mAP']:.4f}")
+            if ap is not None:
+                w(f"  COCO AP - mAP50: {md['mAP50']:.4f} | mAP50-95: {md['mAP50-95']:.4f}")
             w(f"  Detection - TP: {md['true_positives']} | FP: {md['false_positives']} | FN: {md['false_negatives']}")
             w(f"  LR: {optimizer.param_groups[0]['lr']:.6f}")
             w("=" * 80 + "\n")
+    return md

@@ -252,6 +252,18 @@ size_t yolo_val_workspace_bytes(int N, int M, int top_k);
 int yolo_val_select(const void* y, int dtype, int N, int nc, int M, float conf, int top_k, float* out, int* out_count, void* workspace, hipStream_t st);
 int yolo_val_match(const float* pred, const int* count, int N, int top_k, const float* gt, const int* gt_off, double iou_thr, int nc, int skip_empty_gt, long long* counters, int* status, hipStream_t st);
 
+/* ---- COCO average precision on device, beside the reference's `"mAP"` of DetectionMetrics.compute
+   (src/training/metrics.py:159-191: a class-mean precision at one IoU threshold and one confidence cut).
+   yolo_ap_match: COCOeval.evaluateImg without crowd / ignore regions for one batch of yolo_nms rows det fp32 [N][K][6]
+   (x1, y1, x2, y2, score, cls; descending score), one wave per image: per threshold t (iou_thr: n_thr doubles on the device,
+   1 <= n_thr <= 10) a row takes the free target of its class with the largest double IoU >= min(thr_t, 1 - 1e-10), the highest
+   index among equal IoUs.  key int64 [N][K] = (cls << 32) | (0xFFFFFFFF - ord(score)), nc << 32 for ignored rows; tp uint32
+   [N][K], bit t = matched at t; gt_count int64 [nc] accumulated; status int32 [1] = 1 if an image had more than 1024 targets.
+   yolo_ap_curve: COCOeval.accumulate for area "all" on the D < 2^31 rows sorted ascending by key (stable): precision double
+   [nc][n_thr][101] at the recall thresholds rec_thr (101 doubles on the device), -1 for a class without targets */
+int yolo_ap_match(const float* det, const int* count, int N, int K, const float* gt, const int* gt_off, const double* iou_thr, int n_thr, int nc, long long* key, unsigned* tp, long long* gt_count, int* status, hipStream_t st);
+int yolo_ap_curve(const long long* key, const unsigned* tp, long D, const long long* gt_count, const double* rec_thr, int nc, int n_thr, double* precision, hipStream_t st);
+
 /* ---- on-device input pipeline: the reference's training / validation transform (src/data/transforms.py:4-24:
    horizontal flip, Resize((S,S)) bilinear + antialias, ColorJitter, ToDtype(scale), Normalize) for a batch of decoded uint8 HWC
    images of different sizes in one launch sequence; random decisions are drawn on the host (table records) */
