@@ -18,6 +18,8 @@
 // four resized tiles of the batch's own images around a centre, fill elsewhere; the colour chain behind it is the same.
 // Affine warp (no reference counterpart; opt-in): k_affine gathers the finished canvas of the resize or mosaic launch through
 // an inverse 2x3 matrix, bilinear with a constant `fill` border, into a second staging buffer; the colour chain runs on that.
+// MixUp (no reference counterpart; opt-in): k_mixup blends the finished canvas of an output with the finished, unmixed canvas of
+// another output of the same batch, streaming from one staging buffer into the other; the colour chain runs on the mixed one.
 #include "common.h"
 
 struct PrepImage {
@@ -42,6 +44,10 @@ struct MosaicTile {
 // the inverse map of one output's warp, canvas <- output, in continuous coordinates (pixel i covers [i, i + 1)): the six fp32
 // values the host rounded once from the float64 inverse of the forward matrix
 struct AffineRec { float a00, a01, b0, a10, a11, b1; };
+
+// the mix of one output: the output of the same batch whose finished, unmixed canvas is blended in, and the share r of the
+// output's own canvas; partner = the output's own index means "not mixed" (a copy: no partner is read)
+struct MixRec { int partner; float r; };
 
 namespace {
 
@@ -162,6 +168,49 @@ __global__ __launch_bounds__(256) void k_affine(const unsigned char* __restrict_
 #pragma unroll
     for (int c = 0; c < 3; ++c)
         stage2[(long)n * 3 * hw + c * hw + (long)oy * S + ox] = (unsigned char)fminf(fmaxf(floorf(acc[c] + 0.5f), 0.f), 255.f);
+}
+
+// one mixed level.  Operation order (every operation rounds once; no contraction in this file):
+//   level = clamp(floor((r * a + q * b) + 0.5f), 0, 255) with q = 1.0f - r, as resize_pixel quantises
+// r = 1 gives 1 * a + 0 * b = a and r = 0 gives b, exactly
+__device__ __forceinline__ unsigned mix_level(unsigned a, unsigned b, float r, float q) {
+    return (unsigned)fminf(fmaxf(floorf((r * (float)a + q * (float)b) + 0.5f), 0.f), 255.f);
+}
+
+__device__ __forceinline__ unsigned mix_word(unsigned a, unsigned b, float r, float q) {     // four levels of one dword
+    unsigned o = 0;
+#pragma unroll
+    for (int k = 0; k < 32; k += 8) o |= mix_level((a >> k) & 255u, (b >> k) & 255u, r, q) << k;
+    return o;
+}
+
+// mixup: output n = r * (canvas n) + (1 - r) * (canvas of its partner), a stream over the B = 3 S^2 bytes of every image
+// from `in` (the finished, unmixed canvases) to `out` (another buffer: two outputs that choose each other both read unmixed
+// canvases).  blockIdx.y is the image, so the record is one load per workgroup and "no partner" (partner == n: a copy that
+// reads nothing else) is a uniform branch.  V = 16: one 16-byte vector per lane from each canvas and one store; the host takes
+// it when B % 16 == 0 and both buffers are 16-byte aligned, so that every image base is.  V = 1 otherwise: the same levels
+template <int V>
+__global__ __launch_bounds__(256) void k_mixup(const unsigned char* __restrict__ in, const MixRec* __restrict__ recs,
+                                              unsigned char* __restrict__ out, long B) {
+    const int n = blockIdx.y;
+    const MixRec m = recs[n];
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (i >= B) return;                                            // B % V == 0: a lane's V bytes are all inside or all outside
+    const unsigned char* a = in + (long)n * B + i;
+    const unsigned char* b = in + (long)m.partner * B + i;
+    unsigned char* o = out + (long)n * B + i;
+    const float r = m.r, q = 1.0f - m.r;
+    if (V == 16) {
+        uint4 va = *(const uint4*)a;
+        if (m.partner != n) {
+            const uint4 vb = *(const uint4*)b;
+            va.x = mix_word(va.x, vb.x, r, q); va.y = mix_word(va.y, vb.y, r, q);
+            va.z = mix_word(va.z, vb.z, r, q); va.w = mix_word(va.w, vb.w, r, q);
+        }
+        *(uint4*)o = va;
+    } else {
+        *o = m.partner != n ? (unsigned char)mix_level(*a, *b, r, q) : *a;
+    }
 }
 
 __device__ __forceinline__ float gray_of(float r, float g, float b) { return floorf(0.2989f * r + 0.587f * g + 0.114f * b); }
@@ -288,6 +337,17 @@ int yolo_affine_fill(void* table_host, int index, float a00, float a01, float b0
     return YOLO_OK;
 }
 
+int yolo_mix_bytes(void) { return (int)sizeof(MixRec); }
+
+// fill record `index` of the host-side mix table of a batch of N outputs: partner inside the batch (partner == index: not
+// mixed), r finite and in [0, 1] (a NaN fails both comparisons)
+int yolo_mix_fill(void* table_host, int index, int partner, float r, int N) {
+    if (index < 0 || index >= N || partner < 0 || partner >= N || !(r >= 0.f && r <= 1.f)) return YOLO_ERR_ARG;
+    MixRec& m = ((MixRec*)table_host)[index];
+    m.partner = partner; m.r = r;
+    return YOLO_OK;
+}
+
 }  // extern "C"
 
 // the colour chain on the staging buffer: per jitter slot a gray-mean reduction and that slot's op, the last launch
@@ -360,6 +420,39 @@ int yolo_image_prep_affine(const void* src, const void* tiles_dev, const void* t
     hipLaunchKernelGGL(k_affine, dim3(ceil_div(S, 32), ceil_div(S, 8), N), dim3(256), 0, st, (const unsigned char*)stage,
                        (const AffineRec*)affine_dev, (unsigned char*)stage2, S, fill);
     return color_chain(imgs, N, S, jitter, stage2, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+}
+
+// the same with a mixup between the finished canvas and the colour chain: tiles_dev = nullptr -> the plain resize, else the mosaic;
+// affine_dev = nullptr -> no warp.  mix_dev: [N] yolo_mix_fill records.  Two uint8 stages, always: without the warp the canvas
+// is written to stage, mixed into stage2, and the colour chain runs on stage2; with it k_affine writes stage2, the mix goes
+// back into stage (k_affine has finished reading it: stream order) and the colour chain runs on stage
+int yolo_image_prep_mixup(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, const void* mix_dev,
+                          int N, int S, int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype,
+                          float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
+    if (N <= 0 || N > 65535 || S <= 0 || fill < 0 || fill > 255 || mix_dev == nullptr || stage == nullptr || stage2 == nullptr ||
+        stage2 == stage)
+        return YOLO_ERR_ARG;
+    const PrepImage* imgs = (const PrepImage*)table_dev;
+    if (tiles_dev == nullptr)
+        hipLaunchKernelGGL(k_resize_flip, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src, imgs,
+                           (unsigned char*)stage, S);
+    else
+        hipLaunchKernelGGL(k_mosaic, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src,
+                           (const MosaicTile*)tiles_dev, (unsigned char*)stage, S, fill);
+    void *canvas = stage, *mixed = stage2;
+    if (affine_dev != nullptr) {
+        hipLaunchKernelGGL(k_affine, dim3(ceil_div(S, 32), ceil_div(S, 8), N), dim3(256), 0, st, (const unsigned char*)stage,
+                           (const AffineRec*)affine_dev, (unsigned char*)stage2, S, fill);
+        canvas = stage2; mixed = stage;
+    }
+    const long B = 3L * S * S;
+    if (B % 16 == 0 && (uintptr_t)canvas % 16 == 0 && (uintptr_t)mixed % 16 == 0)
+        hipLaunchKernelGGL(k_mixup<16>, dim3((unsigned)((B / 16 + 255) / 256), N), dim3(256), 0, st, (const unsigned char*)canvas,
+                           (const MixRec*)mix_dev, (unsigned char*)mixed, B);
+    else
+        hipLaunchKernelGGL(k_mixup<1>, dim3((unsigned)((B + 255) / 256), N), dim3(256), 0, st, (const unsigned char*)canvas,
+                           (const MixRec*)mix_dev, (unsigned char*)mixed, B);
+    return color_chain(imgs, N, S, jitter, mixed, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
 }
 
 }  // extern "C"

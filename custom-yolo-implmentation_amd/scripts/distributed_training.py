@@ -125,7 +125,11 @@ def main(args):
             # optional key `data.affine: {degrees, translate, scale, shear, fill, min_box, min_visible, max_aspect, max_boxes,
             # close_epochs}`: a random rotation / scale / shear / translation of the finished canvas (plain or mosaic) with the
             # boxes following, one more launch in the on-device transform (absent = off; the reference has none)
-            affine=data_cfg.get("affine"))
+            affine=data_cfg.get("affine"),
+            # optional key `data.mixup: {p, alpha, max_boxes, close_epochs}`: an output's finished canvas blended with that of
+            # another output of its batch by a Beta(alpha, alpha) ratio, the partner's boxes appended, one more launch in the
+            # on-device transform (absent = off; the reference has none)
+            mixup=data_cfg.get("mixup"))
         # optional key `training.max_grad_norm`: global-norm gradient clipping inside the optimizer step (absent = off).
         # The reference's `training.grad_clip` is dead there (its loop never reads it) and stays ignored here, so a
         # reference config keeps reference numerics.

@@ -23,11 +23,13 @@ class DevicePreppedLoader:
         return len(self.loader)
 
     def set_epoch(self, epoch, num_epochs):
-        """Per-epoch switches of the transform: the mosaic and the affine warp are each off for their last `close_epochs` epochs."""
+        """Per-epoch switches of the transform: the mosaic, the affine warp and the mixup are each off for their last `close_epochs` epochs."""
         if getattr(self.transform, "mosaic", None) is not None:
             self.transform.mosaic_on = epoch < num_epochs - self.transform.mosaic["close_epochs"]
         if getattr(self.transform, "affine", None) is not None:
             self.transform.affine_on = epoch < num_epochs - self.transform.affine["close_epochs"]
+        if getattr(self.transform, "mixup", None) is not None:
+            self.transform.mixup_on = epoch < num_epochs - self.transform.mixup["close_epochs"]
 
     def __iter__(self):
         for images, targets in self.loader:
@@ -106,8 +108,9 @@ class SyntheticDetectionDataset(Dataset):
 
 
 def get_data_loaders(train_parquet, val_parquet, train_images, val_images, batch_size, is_test=False, prefetch_factor=2,
-                     percent=1.0, device="cpu", num_classes=80, res=640, mosaic=None, affine=None):
-    """`mosaic`, `affine`: the optional `data.mosaic` and `data.affine` dicts of BatchTransform, for the training transform only."""
+                     percent=1.0, device="cpu", num_classes=80, res=640, mosaic=None, affine=None, mixup=None):
+    """`mosaic`, `affine`, `mixup`: the optional `data.mosaic`, `data.affine` and `data.mixup` dicts of BatchTransform, for the training
+    transform only."""
     if os.path.exists(train_parquet):
         # the reference's pipeline (src/data/data_loader.py:11-60): workers decode, the transform runs on the device
         from src.data.dataset_loader import DetectionDataset
@@ -122,12 +125,15 @@ def get_data_loaders(train_parquet, val_parquet, train_images, val_images, batch
         kw = dict(num_workers=nw, collate_fn=raw_collate_fn, prefetch_factor=prefetch_factor if nw else None)
         train = DataLoader(train_ds, batch_size=batch_size, shuffle=ts is None, sampler=ts, drop_last=True, **kw)
         val = DataLoader(val_ds, batch_size=batch_size, shuffle=False, sampler=vs, **kw)
-        return DevicePreppedLoader(train, get_train_transforms(res, device, mosaic=mosaic, affine=affine)), DevicePreppedLoader(val, get_val_transforms(res, device))
+        return DevicePreppedLoader(train, get_train_transforms(res, device, mosaic=mosaic, affine=affine, mixup=mixup)), DevicePreppedLoader(val, get_val_transforms(res, device))
     if mosaic is not None:
         raise ValueError("data.mosaic needs decoded images: it composes the batch's uint8 images in the on-device transform, and "
                          f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
     if affine is not None:
         raise ValueError("data.affine needs decoded images: it warps the batch's uint8 canvas in the on-device transform, and "
+                         f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
+    if mixup is not None:
+        raise ValueError("data.mixup needs decoded images: it blends the batch's uint8 canvases in the on-device transform, and "
                          f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
     n = 20 if is_test else 256
     train_ds = SyntheticDetectionDataset(max(batch_size, int(n * percent)), res, num_classes, 1234)

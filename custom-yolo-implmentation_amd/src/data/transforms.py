@@ -13,7 +13,9 @@ batch leaves in the format of src/data/collate.py: (images[N,3,S,S], [target dic
 With `mosaic=` set (opt-in, no reference counterpart), an output is composed of four resized images of its own batch around
 a random centre, in the same launch sequence (`k_mosaic` in the resize launch's place), with its boxes clipped on the host.
 With `affine=` set (opt-in, no reference counterpart), the finished canvas -- plain resize or mosaic -- is warped by a random
-rotation, scale, shear and translation in one more launch (`k_affine`) before the colour chain, and the boxes follow."""
+rotation, scale, shear and translation in one more launch (`k_affine`) before the colour chain, and the boxes follow.
+With `mixup=` set (opt-in, no reference counterpart), the finished canvas of an output is blended with the finished, unmixed
+canvas of another output of its batch in one more launch (`k_mixup`) before the colour chain, and takes that output's boxes too."""
 import math
 
 import numpy as np
@@ -26,10 +28,20 @@ STD = (0.229, 0.224, 0.225)
 MOSAIC_DEFAULTS = dict(p=1.0, gain=(0.4, 1.0), fill=114, min_box=2.0, min_visible=0.1, max_boxes=128, close_epochs=0)
 AFFINE_DEFAULTS = dict(degrees=0.0, translate=0.1, scale=0.5, shear=0.0, fill=114, min_box=2.0, min_visible=0.1, max_aspect=100.0,
                        max_boxes=128, close_epochs=0)
+MIXUP_DEFAULTS = dict(p=0.1, alpha=32.0, max_boxes=128, close_epochs=0)
 
 
 def _uniform(lo, hi):
     return float(torch.empty(1).uniform_(lo, hi))
+
+
+def keep_largest(boxes, area, max_boxes):
+    """The cap of mosaic_boxes, affine_boxes and mixup_boxes: beyond `max_boxes` the rows with the largest `area` stay (ties: the
+    earlier row), in their order."""
+    if boxes.shape[0] > max_boxes:
+        top = torch.sort(area, descending=True, stable=True).indices[:max_boxes]
+        boxes = boxes[torch.sort(top).values]
+    return boxes
 
 
 def mosaic_geometry(draw, i, sizes, flip0, size):
@@ -77,11 +89,7 @@ def mosaic_boxes(record, targets, sizes, size, min_box, min_visible, max_boxes):
         areas.append((cw * ch)[keep])
     if not kept:
         return torch.zeros(0, 5)
-    out, area = torch.cat(kept), torch.cat(areas)
-    if out.shape[0] > max_boxes:
-        top = torch.sort(area, descending=True, stable=True).indices[:max_boxes]
-        out = out[torch.sort(top).values]
-    return out
+    return keep_largest(torch.cat(kept), torch.cat(areas), max_boxes)
 
 
 def affine_matrix(draw, size):
@@ -135,11 +143,14 @@ def affine_boxes(m, boxes5, size, min_box, min_visible, max_aspect, max_boxes):
     gain2 = (mt[0, 0] * mt[1, 1] - mt[0, 1] * mt[1, 0]).abs()
     aspect = torch.maximum(cw / ch, ch / cw)
     keep = (cw >= min_box) & (ch >= min_box) & (cw * ch / (b[:, 2] * b[:, 3] * gain2 + 1e-9) >= min_visible) & (aspect < max_aspect)
-    out, area = torch.stack([nx1, ny1, cw, ch, b[:, 4]], 1)[keep], (cw * ch)[keep]
-    if out.shape[0] > max_boxes:
-        top = torch.sort(area, descending=True, stable=True).indices[:max_boxes]
-        out = out[torch.sort(top).values]
-    return out
+    return keep_largest(torch.stack([nx1, ny1, cw, ch, b[:, 4]], 1)[keep], (cw * ch)[keep], max_boxes)
+
+
+def mixup_boxes(own, partner, max_boxes):
+    """Boxes of a mixed output, (M, 5) float32 (x, y, w, h, label): the output's own final boxes followed by the final boxes its
+    partner's unmixed output carries, every one a full target; beyond max_boxes the largest areas w h stay, in that order."""
+    out = torch.cat([own.float().reshape(-1, 5), partner.float().reshape(-1, 5)])
+    return keep_largest(out, out[:, 2] * out[:, 3], max_boxes)
 
 
 class BatchTransform:
@@ -148,7 +159,7 @@ class BatchTransform:
     items before its transform) or None."""
 
     def __init__(self, train, size=640, device="cuda", dtype=torch.float32, flip_p=0.5, brightness=0.2, contrast=0.2,
-                 saturation=0.2, hue=0.1, mean=MEAN, std=STD, mosaic=None, affine=None):
+                 saturation=0.2, hue=0.1, mean=MEAN, std=STD, mosaic=None, affine=None, mixup=None):
         self.train, self.size, self.device, self.dtype = train, size, torch.device(device), dtype
         self.flip_p, self.jit = flip_p, (brightness, contrast, saturation, hue)
         self.mean, self.std = mean, std
@@ -197,6 +208,23 @@ class BatchTransform:
                                min_visible=float(a["min_visible"]), max_aspect=float(a["max_aspect"]),
                                max_boxes=int(a["max_boxes"]), close_epochs=int(a["close_epochs"]))
         self.affine_on = self.affine is not None
+        # mixup: None (off: today's path, call for call) or a dict of MIXUP_DEFAULTS' keys; `mixup_on` is its per-epoch switch
+        self.mixup = None
+        if mixup is not None:
+            if not train:
+                raise ValueError("mixup is a training augmentation: the validation transform takes none")
+            unknown = set(mixup) - set(MIXUP_DEFAULTS)
+            if unknown:
+                raise ValueError(f"mixup: unknown keys {sorted(unknown)}; expected {sorted(MIXUP_DEFAULTS)}")
+            x = {**MIXUP_DEFAULTS, **mixup}
+            if not 0.0 <= x["p"] <= 1.0:
+                raise ValueError(f"mixup.p must lie in [0, 1], got {x['p']}")
+            if not (x["alpha"] > 0 and math.isfinite(x["alpha"])):
+                raise ValueError(f"mixup.alpha must be positive and finite, got {x['alpha']}")
+            if int(x["max_boxes"]) < 1 or int(x["close_epochs"]) < 0:
+                raise ValueError("mixup: max_boxes >= 1 and close_epochs >= 0")
+            self.mixup = dict(p=float(x["p"]), alpha=float(x["alpha"]), max_boxes=int(x["max_boxes"]), close_epochs=int(x["close_epochs"]))
+        self.mixup_on = self.mixup is not None
         self._pinned = None                 # reused pinned upload buffer (one memcpy per image into it, one async H2D per batch)
         self._uploaded = None
 
@@ -241,6 +269,39 @@ class BatchTransform:
                  _uniform(-a["shear"], a["shear"]), _uniform(0.5 - a["translate"], 0.5 + a["translate"]),
                  _uniform(0.5 - a["translate"], 0.5 + a["translate"])) for _ in range(n)]
 
+    def sample_mixup(self, n):
+        """The mixup decisions of a batch of `n` images, drawn after its `n` sample() calls, after sample_mosaic(n) and after
+        sample_affine(n) where those are on (all three sequences unchanged): nothing for n < 2 (no partner exists); else per
+        output None (not mixed) or (partner, r) -- one `torch.rand(1) < p`, then d = `torch.randint(1, n, (1,))` for the partner
+        (i + d) % n, another output, then r from Beta(alpha, alpha), an fp32 value in [0, 1]."""
+        if self.mixup is None:
+            raise ValueError("sample_mixup: this transform was built without mixup=")
+        x = self.mixup
+        if n < 2:
+            return [None] * n
+        out = []
+        for i in range(n):
+            if not bool(torch.rand(1) < x["p"]):
+                out.append(None)
+                continue
+            d = int(torch.randint(1, n, (1,)))
+            out.append(((i + d) % n, float(torch.distributions.Beta(x["alpha"], x["alpha"]).sample())))
+        return out
+
+    @staticmethod
+    def _mix_records(mixup, n):
+        """Per output None (not mixed) or (partner, r) checked: another output of the batch and an fp32 ratio in [0, 1]."""
+        if len(mixup) != n:
+            raise ValueError(f"mixup: {len(mixup)} records for {n} images")
+        out = []
+        for i, m in enumerate(mixup):
+            if m is not None:
+                if len(m) != 2 or int(m[0]) != m[0] or not 0 <= int(m[0]) < n or int(m[0]) == i or not 0.0 <= float(m[1]) <= 1.0:
+                    raise ValueError(f"mixup record {i}: (partner, r) with another output of the batch and r in [0, 1], got {m!r}")
+                m = (int(m[0]), float(np.float32(m[1])))
+            out.append(m)
+        return out
+
     def _affine_matrices(self, affine, n):
         """Per output the forward 2 x 3 matrix (float64), from draws (six values), ready matrices or None (identity)."""
         if len(affine) != n:
@@ -266,10 +327,10 @@ class BatchTransform:
             raise ValueError("BatchTransform takes decoded RGB images as uint8 (H, W, 3)")
         return t.contiguous()
 
-    def __call__(self, images, targets=None, params=None, mosaic=None, affine=None):
+    def __call__(self, images, targets=None, params=None, mosaic=None, affine=None, mixup=None):
         """`params`: the per-image sample() decisions; `mosaic`: per output None (plain), a sample_mosaic() draw or a
         geometry record (`mosaic_geometry`'s format); `affine`: per output None (identity), a sample_affine() draw or a
-        forward 2 x 3 matrix -- all are drawn here when not given."""
+        forward 2 x 3 matrix; `mixup`: per output None (not mixed) or (partner, r) -- all are drawn here when not given."""
         imgs = [self._as_u8(i) for i in images]
         params = params if params is not None else [self.sample() for _ in imgs]
         if mosaic is not None and self.mosaic is None:
@@ -283,6 +344,13 @@ class BatchTransform:
         if use_affine:
             mats = self._affine_matrices(affine if affine is not None else self.sample_affine(len(imgs)), len(imgs))
             inverse = [affine_record(m) for m in mats]
+        if mixup is not None and self.mixup is None:
+            raise ValueError("mixup records were passed to a BatchTransform built without mixup=")
+        mix = None
+        if self.mixup is not None and (self.mixup_on or mixup is not None):
+            mix = self._mix_records(mixup if mixup is not None else self.sample_mixup(len(imgs)), len(imgs))
+            if all(m is None for m in mix):
+                mix = None                      # nobody mixes: the leaf below is the one a transform without the key takes
         recs, off = [], 0
         for t, (flip, order, fac) in zip(imgs, params):
             h, w = int(t.shape[0]), int(t.shape[1])
@@ -302,7 +370,12 @@ class BatchTransform:
             flat = torch.cat([t.reshape(-1) for t in imgs])
         jitter = self.train and any(len(p[1]) for p in params)
         records = self._mosaic_records(mosaic, recs) if use_mosaic else [None] * len(recs)
-        if use_affine:
+        if mix is not None:
+            fill = self.affine["fill"] if use_affine else self.mosaic["fill"] if use_mosaic else 0
+            batch = ops.image_prep_mixup(flat, recs, self._mosaic_tiles(records, recs) if use_mosaic else None,
+                                         inverse if use_affine else None, [(i, 1.0) if m is None else m for i, m in enumerate(mix)],
+                                         self.size, fill, jitter, self.dtype, self.mean, self.std)
+        elif use_affine:
             tiles = self._mosaic_tiles(records, recs) if use_mosaic else None
             batch = ops.image_prep_affine(flat, recs, tiles, inverse, self.size, self.affine["fill"], jitter, self.dtype, self.mean,
                                           self.std)
@@ -332,6 +405,11 @@ class BatchTransform:
                     new["boxes"] = affine_boxes(mats[i], new["boxes"], self.size, a["min_box"], a["min_visible"], a["max_aspect"],
                                                 a["max_boxes"])
                 out_t.append(new)
+            if mix is not None:                 # the partner's boxes are those of its own unmixed output: read before any is replaced
+                unmixed = [t["boxes"] for t in out_t]
+                for i, m in enumerate(mix):
+                    if m is not None:
+                        out_t[i]["boxes"] = mixup_boxes(unmixed[i], unmixed[m[0]], self.mixup["max_boxes"])
         return batch, out_t
 
     def _mosaic_records(self, mosaic, recs):
@@ -363,8 +441,8 @@ class BatchTransform:
         return out
 
 
-def get_train_transforms(size=640, device="cuda", dtype=torch.float32, mosaic=None, affine=None):
-    return BatchTransform(True, size, device, dtype, mosaic=mosaic, affine=affine)
+def get_train_transforms(size=640, device="cuda", dtype=torch.float32, mosaic=None, affine=None, mixup=None):
+    return BatchTransform(True, size, device, dtype, mosaic=mosaic, affine=affine, mixup=mixup)
 
 
 def get_val_transforms(size=640, device="cuda", dtype=torch.float32):

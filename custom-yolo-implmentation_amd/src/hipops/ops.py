@@ -837,6 +837,41 @@ def image_prep_affine(src_u8, recs, tiles, affine, size, fill, jitter, dtype, me
     return out
 
 
+def image_prep_mixup(src_u8, recs, tiles, affine, mix, size, fill, jitter, dtype, mean, std):
+    """`image_prep` (tiles None), `image_prep_mosaic` (tiles as there) or either behind `image_prep_affine`'s warp (affine as there;
+    None = no warp) with a mixup between the finished canvas and the colour chain.  mix: per output (partner, r): the output becomes
+    r * its own canvas + (1 - r) * the finished, unmixed canvas of output `partner` of the same batch, rounded like the resize;
+    partner = the output's own index leaves it as it is.  The PrepImage table, the tile table, the affine table and the mix table
+    travel in one pinned buffer and one upload."""
+    n = len(recs)
+    if len(mix) != n or (tiles is not None and len(tiles) != n) or (affine is not None and len(affine) != n):
+        raise ValueError(f"image_prep_mixup: {n} records need {n} mix records and, if any, {n} tile sets and {n} affine records")
+    st = _stream(src_u8)
+    rb, tb, ab, mb = (lib.query(q) for q in ("yolo_prep_image_bytes", "yolo_mosaic_tile_bytes", "yolo_affine_bytes", "yolo_mix_bytes"))
+    nt = 4 * n * tb if tiles is not None else 0
+    na = n * ab if affine is not None else 0
+    host = torch.zeros(n * rb + nt + na + n * mb, dtype=torch.uint8).pin_memory()
+    _prep_table_fill(host, recs)
+    if tiles is not None:
+        _tile_table_fill(host.data_ptr() + n * rb, tiles, src_u8.numel(), "image_prep_mixup")
+    for i, a in enumerate(affine if affine is not None else ()):
+        if len(a) != 6:
+            raise ValueError(f"image_prep_mixup: affine record {i} needs six values, got {len(a)}")
+        lib.call("yolo_affine_fill", host.data_ptr() + n * rb + nt, i, *[float(v) for v in a])
+    for i, m in enumerate(mix):
+        if len(m) != 2:
+            raise ValueError(f"image_prep_mixup: mix record {i} is (partner, r), got {m!r}")
+        lib.call("yolo_mix_fill", host.data_ptr() + n * rb + nt + na, i, int(m[0]), float(m[1]), n)
+    table = host.to(src_u8.device, non_blocking=True)
+    stage = torch.empty((2, n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
+    means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
+    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
+    lib.call("yolo_image_prep_mixup", _p(src_u8), _p(table) + n * rb if tiles is not None else 0, _p(table),
+             _p(table) + n * rb + nt if affine is not None else 0, _p(table) + n * rb + nt + na, n, size, int(fill), int(bool(jitter)),
+             _p(stage[0]), _p(stage[1]), _p(means), _p(out), dt(dtype), *[float(v) for v in mean], *[float(v) for v in std], st)
+    return out
+
+
 def head_decode(preds, anchors, strides, nc):
     n, cp, a = preds.shape
     preds = preds.contiguous()

@@ -287,6 +287,17 @@ int yolo_image_prep_mosaic(const void* src, const void* tiles_dev, const void* t
 int yolo_affine_bytes();
 int yolo_affine_fill(void* table_host, int index, float a00, float a01, float b0, float a10, float a11, float b1);
 int yolo_image_prep_affine(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, int N, int S, int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
+/* mixup between the finished canvas and the same colour chain (no reference counterpart: src/data/transforms.py:4-14 has flip, resize and
+   ColorJitter only): output i with the record (partner j != i, ratio r in [0, 1]) becomes, per uint8 element, in fp32, every operation
+   rounding once, level = clamp(floor((r * a + (1.0f - r) * b) + 0.5f), 0, 255), a = the finished canvas of output i (tiles_dev == nullptr:
+   the plain resize, else the mosaic; warped unless affine_dev == nullptr), b = the finished UNMIXED canvas of output j, whatever j's own
+   record says; rounded like the resize.  The colour chain runs on the mixed canvas with the jitter of output i.  mix_dev: [N] records
+   (yolo_mix_fill; it refuses an index or a partner outside [0, N) and an r that is not finite or not in [0, 1]); stage, stage2: two
+   distinct uint8 [N][3][S][S] scratches, both always used.  The record partner = i is a copy that reads no partner and reproduces
+   yolo_image_prep / yolo_image_prep_mosaic / yolo_image_prep_affine bit for bit; r = 1 gives a and r = 0 gives b exactly */
+int yolo_mix_bytes();
+int yolo_mix_fill(void* table_host, int index, int partner, float r, int N);
+int yolo_image_prep_mixup(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, const void* mix_dev, int N, int S, int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
 
 /* ---- hardware self-tests (instruction semantics the tiled kernels assume; tests/test_gpu_selftest.py; no reference counterpart: model_blocks.py:1) */
 int yolo_selftest_tr16(const void* tile_in, void* out, hipStream_t st);

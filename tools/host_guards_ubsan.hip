@@ -1,6 +1,6 @@
 // Host-only sweep of the plan and guard queries for UndefinedBehaviorSanitizer: yolo_conv2d_plan, yolo_conv2d_wgrad_plan,
 // yolo_conv2d_wgrad_ws_elems, yolo_dw_plan, yolo_dw_wgrad_nslab and yolo_stem_conv_eligible are integer arithmetic on
-// caller-supplied ints and call nothing in the HIP runtime.  Built by tests/test_host_guards_ubsan.py from csrc/*.hip with
+// caller-supplied ints and call nothing in the HIP runtime; yolo_mix_fill checks an index, a partner and a ratio before it writes.  Built by tests/test_host_guards_ubsan.py from csrc/*.hip with
 //     hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined
 // (the sanitizer on the host side only) and run there, on the CPU: any report ends the program with a non-zero status.
 // Shapes: the sweep of tests/test_addressing_cpu.py at the largest N under and the smallest N over each limit, then every
@@ -71,6 +71,23 @@ int main() {
     }
     for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) for (int co : ext) { sink += (unsigned long)yolo_stem_conv_eligible(a, b, co); ++calls; }
     for (int co = 0; co <= 256; co += 8) { sink += (unsigned long)yolo_stem_conv_eligible(0, 1, co); ++calls; }
+    // yolo_mix_fill: a record is written only for an index and a partner inside [0, N) and an r in [0, 1]; edge and hostile values
+    {
+        alignas(8) static char table[4 * 8];
+        static const int idx[] = {INT_MIN, -1, 0, 1, 3, 4, INT_MAX};
+        static const float rs[] = {0.f, -0.f, 1.f, 0.5f, 0x1p-149f, 0x1.fffffep-1f, 0x1.000002p+0f, -0x1p-149f, -0.1f, 1.5f, 3.4e38f, -3.4e38f,
+                                   __builtin_inff(), -__builtin_inff(), __builtin_nanf("")};
+        static const int ns[] = {INT_MIN, -1, 0, 1, 4};      // the table has four records: N <= 4
+        long ok = 0;
+        for (int n : ns) for (int i : idx) for (int p : idx) for (float r : rs) {
+            const int rc = yolo_mix_fill(table, i, p, r, n);
+            const bool valid = i >= 0 && i < n && p >= 0 && p < n && r >= 0.f && r <= 1.f;
+            if ((rc == 0) != valid) { printf("yolo_mix_fill(%d, %d, %g, %d) answered %d\n", i, p, (double)r, n, rc); return 1; }
+            ok += rc == 0; sink += (unsigned long)rc; ++calls;
+        }
+        if (yolo_mix_bytes() != 8 || ok == 0) { printf("yolo_mix_bytes / yolo_mix_fill: no record accepted\n"); return 1; }
+        sink += (unsigned long)yolo_mix_bytes(); ++calls;
+    }
     printf("host guards: %ld calls, no undefined behaviour reported (checksum %lu)\n", calls, sink);
     return 0;
 }

@@ -4,14 +4,16 @@
 mosaic, plain, ...), so drift of the box hits both alike.  The mosaic decisions are drawn once and reused, like the plain
 ones, so the windows time the upload and the launches, not the host RNG.
 
-    python tools/mosaic_cost.py [--batches 10] [--rounds 7] [--gain 0.4 1.0] [--plain-only] [--affine]
+    python tools/mosaic_cost.py [--batches 10] [--rounds 7] [--gain 0.4 1.0] [--plain-only] [--affine] [--mixup]
 
 `--gain 1 1` keeps every tile at the plain resize's scale (same taps per pixel as the plain path, fewer pixels sampled):
 with it the difference to the default gain separates the larger antialias footprints of shrunken tiles from the cost of
 the quadrant test and the divergence at the quadrant edges.  `--plain-only` times the plain path alone (a checkout without
 the mosaic).  `--affine` adds the warp's two batches to the alternation: `affine={"degrees": 10, "shear": 2}` behind the plain
 resize and behind the mosaic, decisions drawn once (kernel rows: k_affine beside k_resize_flip / k_mosaic; it reads and writes
-N * 3 * S * S bytes).  Prints one JSON line.  (Kernel rows: run under `rocprofv3 --kernel-trace --stats -d DIR -- python
+N * 3 * S * S bytes).  `--mixup` adds the mixup's batches: `mixup={"p": 1}`, every output mixed with a
+partner drawn once, behind the plain resize and behind mosaic + warp (kernel row: k_mixup; it reads 2 and writes 1 x N * 3 * S * S
+bytes).  Prints one JSON line.  (Kernel rows: run under `rocprofv3 --kernel-trace --stats -d DIR -- python
 tools/mosaic_cost.py --rounds 2` and compare k_resize_flip with k_mosaic.)"""
 import argparse
 import json
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--gain", type=float, nargs=2, default=[0.4, 1.0])
     ap.add_argument("--plain-only", action="store_true")
     ap.add_argument("--affine", action="store_true")
+    ap.add_argument("--mixup", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mosaic_cost.py needs an MI355X")
@@ -76,6 +79,19 @@ def main():
         if not args.plain_only:
             both = BatchTransform(True, size=640, device="cuda", dtype=torch.bfloat16, mosaic={"p": 1.0, "gain": args.gain}, affine=acfg)
             calls["mosaic_affine"] = lambda: both(imgs, params=params, mosaic=draws, affine=warps)
+    if args.mixup:
+        acfg = {"degrees": 10.0, "shear": 2.0}
+        mix = BatchTransform(True, size=640, device="cuda", dtype=torch.bfloat16, mixup={"p": 1.0})
+        pairs = mix.sample_mixup(len(imgs))
+        calls["mixup"] = lambda: mix(imgs, params=params, mixup=pairs)
+        if not args.plain_only:
+            if "mosaic_affine" not in calls:
+                both = BatchTransform(True, size=640, device="cuda", dtype=torch.bfloat16, mosaic={"p": 1.0, "gain": args.gain}, affine=acfg)
+                warps = both.sample_affine(len(imgs))
+                calls["mosaic_affine"] = lambda: both(imgs, params=params, mosaic=draws, affine=warps)
+            every = BatchTransform(True, size=640, device="cuda", dtype=torch.bfloat16, mosaic={"p": 1.0, "gain": args.gain}, affine=acfg,
+                                   mixup={"p": 1.0})
+            calls["mosaic_affine_mixup"] = lambda: every(imgs, params=params, mosaic=draws, affine=warps, mixup=pairs)
     for call in calls.values():
         for _ in range(args.warmup):
             call()
@@ -94,9 +110,11 @@ def main():
     if "mosaic" in times:
         out["gain"] = args.gain
         out["mosaic_over_plain"] = round(out["median_mosaic_ms"] / out["median_plain_ms"], 3)
-    for k in ("affine", "mosaic_affine"):
+    for k in ("affine", "mosaic_affine", "mixup", "mosaic_affine_mixup"):
         if k in times:
             out[f"{k}_over_plain"] = round(out[f"median_{k}_ms"] / out["median_plain_ms"], 3)
+    if "mosaic_affine_mixup" in times:
+        out["mosaic_affine_mixup_over_mosaic_affine"] = round(out["median_mosaic_affine_mixup_ms"] / out["median_mosaic_affine_ms"], 3)
     print(json.dumps(out), flush=True)
 
 
