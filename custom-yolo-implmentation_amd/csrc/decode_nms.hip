@@ -13,6 +13,7 @@
 // fp32 IoU exactly as torchvision: inter / (area_i + area_j - inter), strict >, no eps.
 // Built with -ffp-contract=off: bit-exact index selection needs the un-fused multiply/add order.
 #include "common.h"
+#include "letter_rec.h"
 
 namespace {
 
@@ -497,6 +498,26 @@ __global__ __launch_bounds__(64) void k_val_match(const float* __restrict__ pred
     }
 }
 
+// the inverse of the letterbox on yolo_nms's rows, in place: one thread per row, rows at or past counts[n] are not touched.
+// Every operation rounds once (no contraction in this file):
+//   x' = min(max((x - (float)left) * sx, 0.f), (float)W) for x1 and x2, y' likewise with top, sy and H
+//   conf' = prob ? 1.f / (1.f + expf(-conf)) : conf;  cls unchanged
+__global__ __launch_bounds__(256) void k_rows_to_source(float* __restrict__ rows, const int* __restrict__ counts,
+                                                       const LetterRec* __restrict__ recs, long total, int max_det, int prob) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int n = (int)(i / max_det), j = (int)(i % max_det);
+    if (j >= counts[n]) return;
+    const LetterRec L = recs[n];
+    float* r = rows + i * 6;
+    const float fl = (float)L.left, ft = (float)L.top, fw = (float)L.W, fh = (float)L.H;
+    r[0] = fminf(fmaxf((r[0] - fl) * L.sx, 0.f), fw);
+    r[1] = fminf(fmaxf((r[1] - ft) * L.sy, 0.f), fh);
+    r[2] = fminf(fmaxf((r[2] - fl) * L.sx, 0.f), fw);
+    r[3] = fminf(fmaxf((r[3] - ft) * L.sy, 0.f), fh);
+    if (prob) r[4] = 1.f / (1.f + expf(-r[4]));
+}
+
 }  // namespace
 
 extern "C" {
@@ -580,6 +601,16 @@ int yolo_nms(const void* y, int dtype, int bs, int nc, int M, float conf_thres, 
     }
     rc = hip_status(hipMemcpyAsync(status, overflow, 4, hipMemcpyDeviceToDevice, st));
     if (rc) return rc;
+    return YOLO_LAUNCH_CHECK();
+}
+
+// rows: yolo_nms's out, fp32 [N][max_det][6], mapped in place from the letterboxed canvas to each source image's own pixels;
+// table_dev: the N yolo_letter_fill records of the launch that made the canvas; prob: the score becomes its sigmoid
+int yolo_rows_to_source(float* rows, const int* counts, const void* table_dev, int N, int max_det, int prob, hipStream_t st) {
+    if (N <= 0 || max_det < 1 || rows == nullptr || counts == nullptr || table_dev == nullptr) return YOLO_ERR_ARG;
+    const long total = (long)N * max_det;
+    hipLaunchKernelGGL(k_rows_to_source, dim3(ceil_div(total, 256)), dim3(256), 0, st, rows, counts, (const LetterRec*)table_dev,
+                       total, max_det, prob);
     return YOLO_LAUNCH_CHECK();
 }
 

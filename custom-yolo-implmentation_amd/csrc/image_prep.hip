@@ -20,7 +20,10 @@
 // an inverse 2x3 matrix, bilinear with a constant `fill` border, into a second staging buffer; the colour chain runs on that.
 // MixUp (no reference counterpart; opt-in): k_mixup blends the finished canvas of an output with the finished, unmixed canvas of
 // another output of the same batch, streaming from one staging buffer into the other; the colour chain runs on the mixed one.
+// Letterbox (no reference counterpart; the inference interface `Model.predict`): k_letterbox resizes each source to an integer
+// rectangle inside the canvas, fills the bars and writes the normalised NCHW input in the same launch -- no staging buffer.
 #include "common.h"
+#include "letter_rec.h"
 
 struct PrepImage {
     long off;           // byte offset of the image (uint8 HWC, row stride W*3) in the source buffer
@@ -295,9 +298,50 @@ __global__ __launch_bounds__(256) void k_color(unsigned char* __restrict__ stage
     }
 }
 
+// letterbox: one thread per canvas pixel, straight from the uint8 sources to the model's input.  Inside the record's rectangle
+// the three levels are resize_pixel's (the routine of k_resize_flip and k_mosaic), elsewhere `fill`; the conversion is
+// k_color<T, true>'s, operation for operation, so the launch reproduces k_mosaic + k_color<T, true> bit for bit.  The grid
+// depends on N and S only; the tap loops take their lengths from the record
+template <typename T>
+__global__ __launch_bounds__(256) void k_letterbox(const unsigned char* __restrict__ src, const LetterRec* __restrict__ recs,
+                                                  int S, int fill, T* __restrict__ out, float m0, float m1, float m2, float s0,
+                                                  float s1, float s2) {
+    const int n = blockIdx.z;
+    const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+    if (ox >= S) return;
+    const LetterRec L = recs[n];
+    const int lx = ox - L.left, ly = oy - L.top;
+    unsigned char px[3] = {(unsigned char)fill, (unsigned char)fill, (unsigned char)fill};
+    if (lx >= 0 && lx < L.nw && ly >= 0 && ly < L.nh) resize_pixel(src + L.off, L.H, L.W, 0, ly, lx, L.nh, L.nw, px);
+    const long hw = (long)S * S, i = (long)oy * S + ox;
+    T* o = out + (long)n * 3 * hw;
+    o[i] = from_f<T>(((float)px[0] * (1.f / 255.f) - m0) / s0);
+    o[hw + i] = from_f<T>(((float)px[1] * (1.f / 255.f) - m1) / s1);
+    o[2 * hw + i] = from_f<T>(((float)px[2] * (1.f / 255.f) - m2) / s2);
+}
+
 }  // namespace
 
 extern "C" {
+
+int yolo_letter_bytes(void) { return (int)sizeof(LetterRec); }
+
+// fill record `index` of the host-side letterbox table of a launch on an S x S canvas over a source buffer of `src_bytes`
+// bytes.  Refused: an image that does not lie inside the buffer, a rectangle that leaves the canvas, exactly one of nw, nh
+// being 0, a scale that is not finite and positive (a NaN fails the comparison) -- so every device read lies inside the
+// source buffer.  nw = nh = 0: the blank slot (H, W >= 0, nothing is read)
+int yolo_letter_fill(void* table_host, int index, long off, int H, int W, int nw, int nh, int left, int top, float sx, float sy,
+                     int S, long src_bytes) {
+    if (table_host == nullptr || index < 0 || S <= 0 || off < 0 || off > src_bytes || H < 0 || W < 0) return YOLO_ERR_ARG;
+    if ((long)H * W > (src_bytes - off) / 3) return YOLO_ERR_ARG;                 // off + 3 H W > src_bytes, without overflow
+    if (nw < 0 || nw > S || nh < 0 || nh > S || (nw == 0) != (nh == 0)) return YOLO_ERR_ARG;
+    if (nw > 0 && (H <= 0 || W <= 0)) return YOLO_ERR_ARG;
+    if (left < 0 || top < 0 || left > S - nw || top > S - nh) return YOLO_ERR_ARG;
+    if (!(sx > 0.f && sx - sx == 0.f && sy > 0.f && sy - sy == 0.f)) return YOLO_ERR_ARG;
+    LetterRec& r = ((LetterRec*)table_host)[index];
+    r.off = off; r.H = H; r.W = W; r.nw = nw; r.nh = nh; r.left = left; r.top = top; r.sx = sx; r.sy = sy;
+    return YOLO_OK;
+}
 
 int yolo_prep_image_bytes(void) { return (int)sizeof(PrepImage); }
 
@@ -453,6 +497,18 @@ int yolo_image_prep_mixup(const void* src, const void* tiles_dev, const void* ta
         hipLaunchKernelGGL(k_mixup<1>, dim3((unsigned)((B + 255) / 256), N), dim3(256), 0, st, (const unsigned char*)canvas,
                            (const MixRec*)mix_dev, (unsigned char*)mixed, B);
     return color_chain(imgs, N, S, jitter, mixed, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+}
+
+// letterbox of N sources into the model's input in one launch: src as above, table_dev = N yolo_letter_fill records, out:
+// [N][3][S][S] of out_dtype
+int yolo_letterbox(const void* src, const void* table_dev, int N, int S, int fill, void* out, int out_dtype, float m0, float m1,
+                   float m2, float s0, float s1, float s2, hipStream_t st) {
+    if (N <= 0 || N > 65535 || S <= 0 || S > 65535 || fill < 0 || fill > 255 || table_dev == nullptr || out == nullptr)
+        return YOLO_ERR_ARG;
+    YOLO_DISPATCH_T(out_dtype, hipLaunchKernelGGL((k_letterbox<T>), dim3(ceil_div(S, 256), S, N), dim3(256), 0, st,
+                                                  (const unsigned char*)src, (const LetterRec*)table_dev, S, fill, (T*)out, m0, m1,
+                                                  m2, s0, s1, s2));
+    return YOLO_LAUNCH_CHECK();
 }
 
 }  // extern "C"

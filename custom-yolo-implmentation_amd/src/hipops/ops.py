@@ -872,6 +872,52 @@ def image_prep_mixup(src_u8, recs, tiles, affine, mix, size, fill, jitter, dtype
     return out
 
 
+def letter_table(recs, size, src_bytes):
+    """The LetterRec records `recs` = [(offset, H, W, nw, nh, left, top, sx, sy)] of a launch on a `size` x `size` canvas over a
+    source buffer of `src_bytes` bytes -> the pinned host table; yolo_letter_fill refuses a record by which the kernel would read
+    outside the buffer or write outside the canvas (nw = nh = 0: a blank slot, all fill)."""
+    rb = lib.query("yolo_letter_bytes")
+    host = torch.zeros(len(recs) * rb, dtype=torch.uint8).pin_memory()
+    for i, r in enumerate(recs):
+        if len(r) != 9:
+            raise ValueError(f"letterbox: record {i} is (offset, H, W, nw, nh, left, top, sx, sy), got {r!r}")
+        lib.call("yolo_letter_fill", host.data_ptr(), i, *[int(v) for v in r[:7]], float(r[7]), float(r[8]), int(size),
+                 int(src_bytes))
+    return host
+
+
+def letterbox(src_u8, recs, size, fill, dtype, mean, std):
+    """Batch of decoded uint8 HWC images (flat device buffer `src_u8`) -> normalised (N, 3, size, size) tensor of `dtype`, every
+    image resized to its record's (nh, nw) by `image_prep`'s filter and placed at (left, top), `fill` elsewhere: one launch, no
+    staging buffer.  recs: the records of `letter_table` (pinned table, one upload), or a table already on the device (a
+    captured graph's static one)."""
+    st = _stream(src_u8)
+    if isinstance(recs, torch.Tensor):
+        table = recs
+        if table.dtype != torch.uint8 or table.device != src_u8.device or table.numel() % lib.query("yolo_letter_bytes"):
+            raise ValueError("letterbox: a device table is the uint8 image of letter_table on the source's device")
+        n = table.numel() // lib.query("yolo_letter_bytes")
+    else:
+        n = len(recs)
+        table = letter_table(recs, size, src_u8.numel()).to(src_u8.device, non_blocking=True)
+    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
+    lib.call("yolo_letterbox", _p(src_u8), _p(table), n, int(size), int(fill), _p(out), dt(dtype), *[float(v) for v in mean],
+             *[float(v) for v in std], st)
+    return out
+
+
+def rows_to_source(rows, counts, table, prob):
+    """`nms` rows fp32 [N][max_det][6] on the letterboxed canvas -> in each source image's own pixels, in place: boxes moved by
+    the pad, scaled per axis and clipped to the image, the score's sigmoid if `prob`; rows at or past counts[n] stay.
+    table: the device image of `letter_table` that made the canvas."""
+    n, max_det, six = rows.shape
+    assert six == 6 and rows.dtype == torch.float32 and rows.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.numel() == n and counts.is_contiguous()
+    assert table.dtype == torch.uint8 and table.device == rows.device and table.numel() == n * lib.query("yolo_letter_bytes")
+    lib.call("yolo_rows_to_source", _p(rows), _p(counts), _p(table), n, max_det, int(bool(prob)), _stream(rows))
+    return rows
+
+
 def head_decode(preds, anchors, strides, nc):
     n, cp, a = preds.shape
     preds = preds.contiguous()

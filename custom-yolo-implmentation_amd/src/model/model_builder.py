@@ -26,6 +26,8 @@ class Model(nn.Module):
     # inference() replays forward + decode as one hipGraph per input shape (src/model/infer_graph.py); False, or
     # YOLO_INFER_GRAPH=0 in the environment, issues the launches one by one as forward() does
     graph_inference = os.environ.get("YOLO_INFER_GRAPH", "1") == "1"
+    # predict()'s default canvas: the square side the reference trains and infers at (its config.yaml's input_size)
+    input_size = 640
 
     def __init__(self, width: List[int], depth: List[int], csp: List[bool], num_classes: int):
         super().__init__()
@@ -42,6 +44,7 @@ class Model(nn.Module):
                 m._count_batches = False
         self._infer_graphs = None
         self._bn_convs = None
+        self._predict_pinned = None              # predict()'s reused pinned upload buffer
 
     def _apply(self, fn, *args, **kwargs):       # .to() / .half() / .cuda(): new storages -- captured graphs point at the old
         self._infer_graphs = None
@@ -117,13 +120,7 @@ class Model(nn.Module):
     def inference(self, image, conf_thres=0.25, iou_thres=0.45):
         """Detections [x1,y1,x2,y2,conf,cls] per image; class scores are the raw logits, as in the
         reference (:115-139).  Decode (DFL expectation -> xywh -> *stride) is one fused kernel."""
-        graphs = None
-        if self.graph_inference:
-            if self._infer_graphs is None:
-                self._infer_graphs = InferenceGraphs()
-            graphs = self._infer_graphs
-        if graphs is None or not graphs.all_eval(self):
-            self.eval()
+        graphs = self._graphs()
         if isinstance(image, str):
             from PIL import Image
             image = Image.open(image).convert("RGB")
@@ -148,3 +145,77 @@ class Model(nn.Module):
             preds, anchors, strides = self.forward(image)
             y = ops.head_decode(preds, anchors, strides, self.head.nc)
             return non_max_suppression(y, conf_thres=conf_thres, iou_thres=iou_thres, nc=self.num_classes)
+
+    def _graphs(self):
+        """The replayed-inference state (None: graph_inference is off), with every module put into eval mode."""
+        graphs = None
+        if self.graph_inference:
+            if self._infer_graphs is None:
+                self._infer_graphs = InferenceGraphs()
+            graphs = self._infer_graphs
+        if graphs is None or not graphs.all_eval(self):
+            self.eval()
+        return graphs
+
+    def predict(self, images, conf=0.25, iou=0.45, max_det=300, classes=None, agnostic=False, size=None, scaleup=True, batch=None):
+        """Detections for pictures of any sizes, in each picture's own pixels (no reference counterpart; `inference` above keeps
+        the reference's semantics).  images: one image or a list of images, each a path, a PIL image, a numpy array or a torch
+        uint8 tensor (arrays and tensors HWC, RGB).  Every picture is letterboxed onto a `size` x `size` canvas (default
+        `input_size`): resized by one gain to an integer size, centred, grey bars (`scaleup=False`: never enlarged).  `conf` is
+        a PROBABILITY in (0, 1) -- the NMS runs on the logits at log(conf / (1 - conf)) -- and the returned score is the sigmoid
+        of the class logit.  -> one (n_i, 6) fp32 tensor [x1, y1, x2, y2, confidence, class] per picture, cloned.
+        `batch=k` runs the pictures in chunks of k slots (a short last chunk is padded with blank slots), so lists of any
+        length replay one captured graph.  One chunk = one upload of the packed uint8 sources, one replay of letterbox ->
+        forward -> decode -> NMS -> map back (src/model/infer_graph.py; launch by launch where `inference` would be), one sync."""
+        import math
+
+        from src.data.letterbox import letterbox_records
+        from src.data.transforms import BatchTransform
+        if not 0.0 < conf < 1.0:
+            raise ValueError(f"predict: conf is a probability in (0, 1), got {conf}")
+        if not 0.0 <= iou <= 1.0:
+            raise ValueError(f"predict: iou lies in [0, 1], got {iou}")
+        if int(max_det) < 1 or (batch is not None and int(batch) < 1):
+            raise ValueError("predict: max_det and batch are at least 1")
+        size = int(size) if size is not None else int(self.input_size)
+        classes = tuple(int(c) for c in classes) if classes is not None else None
+        if not isinstance(images, (list, tuple)):
+            images = [images]
+        imgs = []
+        for im in images:
+            if isinstance(im, str):
+                from PIL import Image
+                im = Image.open(im)
+            try:
+                imgs.append(BatchTransform._as_u8(im))
+            except ValueError:
+                raise ValueError("predict: an image is a path, a PIL image or a uint8 (H, W, 3) RGB array / tensor") from None
+        param = next(self.parameters())
+        if not param.is_cuda:
+            raise RuntimeError("predict runs on the GPU: the product path has no CPU fallback")
+        graphs = self._graphs()
+        thres = math.log(conf / (1.0 - conf))
+        slots = int(batch) if batch is not None else len(imgs)
+        out = []
+        with torch.no_grad():
+            for lo in range(0, len(imgs), max(1, slots)):
+                chunk = imgs[lo:lo + slots]
+                recs, nbytes = letterbox_records([(t.shape[0], t.shape[1]) for t in chunk], size, scaleup, slots)
+                if self._predict_pinned is None or self._predict_pinned.numel() < nbytes:
+                    self._predict_pinned = torch.empty(max(1 << 20, int(nbytes * 1.25)), dtype=torch.uint8).pin_memory()
+                pinned = self._predict_pinned               # (free again: every chunk ends in a host sync behind its upload)
+                for t, r in zip(chunk, recs):
+                    pinned[r[0]:r[0] + t.numel()].copy_(t.reshape(-1))
+                table = ops.letter_table(recs, size, nbytes)
+                args = (size, param.dtype, thres, iou, int(max_det), bool(agnostic), classes)
+                res = graphs.run_predict(self, pinned, nbytes, table, *args) if graphs is not None else None
+                if res is None:
+                    src = pinned[:nbytes].to(param.device, non_blocking=True)
+                    rows, counts, status = InferenceGraphs.predict_launches(self, src, table.to(param.device, non_blocking=True), *args)
+                    host = torch.cat((counts, status)).tolist()
+                    if host[-1]:
+                        raise RuntimeError("yolo_nms: more candidates than the kernel capacity; raise conf")
+                    res = rows, host[:-1]
+                rows, counts = res
+                out += [rows[i, :counts[i]] for i in range(len(chunk))]     # (a blank slot's rows are dropped)
+        return out

@@ -243,6 +243,11 @@ int yolo_dfl_expect(const void* x, void* y, int B, int A, int dtype, hipStream_t
 int yolo_nms_capacity(int M, int nc, int multi_label);
 size_t yolo_nms_workspace_bytes(int bs, int M, int nc, int multi_label);
 int yolo_nms(const void* y, int dtype, int bs, int nc, int M, float conf_thres, float iou_thres, const int* classes, int n_classes, int agnostic, int multi_label, int max_det, float* out, int* out_count, int* status, void* workspace, hipStream_t st);
+/* the inverse of yolo_letterbox on yolo_nms's rows (no reference counterpart: model_builder.py:115-139 returns boxes in the 640 x 640 input's
+   coordinates), in place on out fp32 [N][max_det][6]; rows at or past counts[n] are not touched.  table_dev: the N yolo_letter_fill records.
+   In fp32, every operation rounding once: x' = min(max((x - left) * sx, 0), W) for x1 and x2, y' likewise with top, sy and H;
+   conf' = prob ? 1 / (1 + expf(-conf)) : conf; the class stays */
+int yolo_rows_to_source(float* rows, const int* counts, const void* table_dev, int N, int max_det, int prob, hipStream_t st);
 
 /* ---- validation on device: decode_predictions' per-image select (train_model.py:14-142: sigmoid best class,
    `>= conf`, top-k by score; rows = cx, cy, w, h, cls, score) on yolo_head_decode's output, and DetectionMetrics.update
@@ -298,6 +303,15 @@ int yolo_image_prep_affine(const void* src, const void* tiles_dev, const void* t
 int yolo_mix_bytes();
 int yolo_mix_fill(void* table_host, int index, int partner, float r, int N);
 int yolo_image_prep_mixup(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, const void* mix_dev, int N, int S, int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
+/* letterbox straight into the model's input (no reference counterpart: model_builder.py:115-139 stretches a picture to 640 x 640 through
+   src/data/transforms.py:16-24): image i, resized to (nh, nw) by the filter above, lies at (left, top) of the S x S canvas, `fill` elsewhere,
+   and the canvas is converted like the colour chain's last launch, (level / 255 - mean) / std, to NCHW of out_dtype -- one launch, no uint8
+   staging; bit for bit what yolo_image_prep_mosaic gives for the same rectangle.  (sx, sy) = (W / nw, H / nh) in fp32 serve
+   yolo_rows_to_source.  yolo_letter_fill refuses (YOLO_ERR_ARG) an image outside [0, src_bytes), nw or nh outside [0, S], exactly one of
+   them 0, a rectangle that leaves the canvas and a scale that is not finite and positive; nw = nh = 0 is a blank slot (all fill, nothing read) */
+int yolo_letter_bytes();
+int yolo_letter_fill(void* table_host, int index, long off, int H, int W, int nw, int nh, int left, int top, float sx, float sy, int S, long src_bytes);
+int yolo_letterbox(const void* src, const void* table_dev, int N, int S, int fill, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
 
 /* ---- hardware self-tests (instruction semantics the tiled kernels assume; tests/test_gpu_selftest.py; no reference counterpart: model_blocks.py:1) */
 int yolo_selftest_tr16(const void* tile_in, void* out, hipStream_t st);
