@@ -421,6 +421,35 @@ static int color_chain(const PrepImage* imgs, int N, int S, int jitter, void* st
     return YOLO_LAUNCH_CHECK();
 }
 
+// the one launch sequence of the four yolo_image_prep* entries (a new stage is added HERE, once): the canvas into `stage` (k_mosaic
+// when tiles_dev is given, else k_resize_flip); with affine_dev, k_affine into the other buffer; with mix_dev, k_mixup into the buffer
+// that is free by then (the kernel before it has finished reading it: stream order); the colour chain where the finished canvas lies.
+// stage2 is not touched when both tables are null.  The entries refuse bad arguments, each its own; nothing is checked here
+static int prep_run(const void* src, const void* table_dev, const void* tiles_dev, const void* affine_dev, const void* mix_dev, int N,
+                    int S, int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype, float m0, float m1,
+                    float m2, float s0, float s1, float s2, hipStream_t st) {
+    const PrepImage* imgs = (const PrepImage*)table_dev;
+    const unsigned char* in = (const unsigned char*)src;
+    unsigned char *canvas = (unsigned char*)stage, *other = (unsigned char*)stage2;
+    const dim3 rows(ceil_div(S, 256), S, N), blk(256);
+    if (tiles_dev == nullptr) hipLaunchKernelGGL(k_resize_flip, rows, blk, 0, st, in, imgs, canvas, S);
+    else hipLaunchKernelGGL(k_mosaic, rows, blk, 0, st, in, (const MosaicTile*)tiles_dev, canvas, S, fill);
+    if (affine_dev != nullptr) {
+        hipLaunchKernelGGL(k_affine, dim3(ceil_div(S, 32), ceil_div(S, 8), N), blk, 0, st, canvas, (const AffineRec*)affine_dev, other, S,
+                           fill);
+        canvas = other; other = (unsigned char*)stage;
+    }
+    if (mix_dev != nullptr) {
+        const long B = 3L * S * S;
+        if (B % 16 == 0 && (uintptr_t)canvas % 16 == 0 && (uintptr_t)other % 16 == 0)
+            hipLaunchKernelGGL(k_mixup<16>, dim3((unsigned)((B / 16 + 255) / 256), N), blk, 0, st, canvas, (const MixRec*)mix_dev, other, B);
+        else
+            hipLaunchKernelGGL(k_mixup<1>, dim3((unsigned)((B + 255) / 256), N), blk, 0, st, canvas, (const MixRec*)mix_dev, other, B);
+        canvas = other;
+    }
+    return color_chain(imgs, N, S, jitter, canvas, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+}
+
 extern "C" {
 
 // src: all images of the batch, uint8 HWC, back to back (table[i].off); stage: uint8 scratch [N][3][S][S]; means: fp32
@@ -428,10 +457,8 @@ extern "C" {
 int yolo_image_prep(const void* src, const void* table_dev, int N, int S, int jitter, void* stage, float* means, void* out,
                     int out_dtype, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
     if (N <= 0 || S <= 0) return YOLO_ERR_ARG;
-    const PrepImage* imgs = (const PrepImage*)table_dev;
-    hipLaunchKernelGGL(k_resize_flip, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src, imgs,
-                       (unsigned char*)stage, S);
-    return color_chain(imgs, N, S, jitter, stage, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+    return prep_run(src, table_dev, nullptr, nullptr, nullptr, N, S, 0, jitter, stage, nullptr, means, out, out_dtype, m0, m1, m2, s0,
+                    s1, s2, st);
 }
 
 // the same with a mosaic in front of the colour chain: tiles_dev = [N][4] MosaicTile records (yolo_mosaic_tile_fill),
@@ -440,63 +467,33 @@ int yolo_image_prep_mosaic(const void* src, const void* tiles_dev, const void* t
                            void* stage, float* means, void* out, int out_dtype, float m0, float m1, float m2, float s0, float s1,
                            float s2, hipStream_t st) {
     if (N <= 0 || S <= 0 || fill < 0 || fill > 255) return YOLO_ERR_ARG;
-    hipLaunchKernelGGL(k_mosaic, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src,
-                       (const MosaicTile*)tiles_dev, (unsigned char*)stage, S, fill);
-    return color_chain((const PrepImage*)table_dev, N, S, jitter, stage, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+    return prep_run(src, table_dev, tiles_dev, nullptr, nullptr, N, S, fill, jitter, stage, nullptr, means, out, out_dtype, m0, m1, m2,
+                    s0, s1, s2, st);
 }
 
-// the same with an affine warp between the canvas and the colour chain: tiles_dev = nullptr -> k_resize_flip writes the canvas,
-// else k_mosaic; k_affine gathers it through affine_dev ([N] yolo_affine_fill records) into stage2 ([N][3][S][S] uint8, not
-// overlapping stage), and the colour chain runs on stage2.  `fill` is the level of the mosaic's empty quadrants and of the
-// warp's uncovered pixels
+// the same with an affine warp between the canvas and the colour chain: k_affine gathers the canvas through affine_dev ([N]
+// yolo_affine_fill records) into stage2 ([N][3][S][S] uint8, not overlapping stage), and the colour chain runs on stage2.  `fill` is
+// the level of the mosaic's empty quadrants and of the warp's uncovered pixels
 int yolo_image_prep_affine(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, int N, int S,
                            int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype, float m0,
                            float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
     if (N <= 0 || S <= 0 || fill < 0 || fill > 255 || affine_dev == nullptr || stage2 == nullptr || stage2 == stage)
         return YOLO_ERR_ARG;
-    const PrepImage* imgs = (const PrepImage*)table_dev;
-    if (tiles_dev == nullptr)
-        hipLaunchKernelGGL(k_resize_flip, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src, imgs,
-                           (unsigned char*)stage, S);
-    else
-        hipLaunchKernelGGL(k_mosaic, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src,
-                           (const MosaicTile*)tiles_dev, (unsigned char*)stage, S, fill);
-    hipLaunchKernelGGL(k_affine, dim3(ceil_div(S, 32), ceil_div(S, 8), N), dim3(256), 0, st, (const unsigned char*)stage,
-                       (const AffineRec*)affine_dev, (unsigned char*)stage2, S, fill);
-    return color_chain(imgs, N, S, jitter, stage2, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+    return prep_run(src, table_dev, tiles_dev, affine_dev, nullptr, N, S, fill, jitter, stage, stage2, means, out, out_dtype, m0, m1,
+                    m2, s0, s1, s2, st);
 }
 
 // the same with a mixup between the finished canvas and the colour chain: tiles_dev = nullptr -> the plain resize, else the mosaic;
-// affine_dev = nullptr -> no warp.  mix_dev: [N] yolo_mix_fill records.  Two uint8 stages, always: without the warp the canvas
-// is written to stage, mixed into stage2, and the colour chain runs on stage2; with it k_affine writes stage2, the mix goes
-// back into stage (k_affine has finished reading it: stream order) and the colour chain runs on stage
+// affine_dev = nullptr -> no warp.  mix_dev: [N] yolo_mix_fill records.  Two uint8 stages, always (the chain ends on stage2 without the
+// warp, on stage with it)
 int yolo_image_prep_mixup(const void* src, const void* tiles_dev, const void* table_dev, const void* affine_dev, const void* mix_dev,
                           int N, int S, int fill, int jitter, void* stage, void* stage2, float* means, void* out, int out_dtype,
                           float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
     if (N <= 0 || N > 65535 || S <= 0 || fill < 0 || fill > 255 || mix_dev == nullptr || stage == nullptr || stage2 == nullptr ||
         stage2 == stage)
         return YOLO_ERR_ARG;
-    const PrepImage* imgs = (const PrepImage*)table_dev;
-    if (tiles_dev == nullptr)
-        hipLaunchKernelGGL(k_resize_flip, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src, imgs,
-                           (unsigned char*)stage, S);
-    else
-        hipLaunchKernelGGL(k_mosaic, dim3(ceil_div(S, 256), S, N), dim3(256), 0, st, (const unsigned char*)src,
-                           (const MosaicTile*)tiles_dev, (unsigned char*)stage, S, fill);
-    void *canvas = stage, *mixed = stage2;
-    if (affine_dev != nullptr) {
-        hipLaunchKernelGGL(k_affine, dim3(ceil_div(S, 32), ceil_div(S, 8), N), dim3(256), 0, st, (const unsigned char*)stage,
-                           (const AffineRec*)affine_dev, (unsigned char*)stage2, S, fill);
-        canvas = stage2; mixed = stage;
-    }
-    const long B = 3L * S * S;
-    if (B % 16 == 0 && (uintptr_t)canvas % 16 == 0 && (uintptr_t)mixed % 16 == 0)
-        hipLaunchKernelGGL(k_mixup<16>, dim3((unsigned)((B / 16 + 255) / 256), N), dim3(256), 0, st, (const unsigned char*)canvas,
-                           (const MixRec*)mix_dev, (unsigned char*)mixed, B);
-    else
-        hipLaunchKernelGGL(k_mixup<1>, dim3((unsigned)((B + 255) / 256), N), dim3(256), 0, st, (const unsigned char*)canvas,
-                           (const MixRec*)mix_dev, (unsigned char*)mixed, B);
-    return color_chain(imgs, N, S, jitter, mixed, means, out, out_dtype, m0, m1, m2, s0, s1, s2, st);
+    return prep_run(src, table_dev, tiles_dev, affine_dev, mix_dev, N, S, fill, jitter, stage, stage2, means, out, out_dtype, m0, m1,
+                    m2, s0, s1, s2, st);
 }
 
 // letterbox of N sources into the model's input in one launch: src as above, table_dev = N yolo_letter_fill records, out:

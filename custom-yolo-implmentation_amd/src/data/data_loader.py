@@ -24,12 +24,10 @@ class DevicePreppedLoader:
 
     def set_epoch(self, epoch, num_epochs):
         """Per-epoch switches of the transform: the mosaic, the affine warp and the mixup are each off for their last `close_epochs` epochs."""
-        if getattr(self.transform, "mosaic", None) is not None:
-            self.transform.mosaic_on = epoch < num_epochs - self.transform.mosaic["close_epochs"]
-        if getattr(self.transform, "affine", None) is not None:
-            self.transform.affine_on = epoch < num_epochs - self.transform.affine["close_epochs"]
-        if getattr(self.transform, "mixup", None) is not None:
-            self.transform.mixup_on = epoch < num_epochs - self.transform.mixup["close_epochs"]
+        for name in ("mosaic", "affine", "mixup"):
+            options = getattr(self.transform, name, None)
+            if options is not None:
+                setattr(self.transform, name + "_on", epoch < num_epochs - options["close_epochs"])
 
     def __iter__(self):
         for images, targets in self.loader:
@@ -126,15 +124,11 @@ def get_data_loaders(train_parquet, val_parquet, train_images, val_images, batch
         train = DataLoader(train_ds, batch_size=batch_size, shuffle=ts is None, sampler=ts, drop_last=True, **kw)
         val = DataLoader(val_ds, batch_size=batch_size, shuffle=False, sampler=vs, **kw)
         return DevicePreppedLoader(train, get_train_transforms(res, device, mosaic=mosaic, affine=affine, mixup=mixup)), DevicePreppedLoader(val, get_val_transforms(res, device))
-    if mosaic is not None:
-        raise ValueError("data.mosaic needs decoded images: it composes the batch's uint8 images in the on-device transform, and "
-                         f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
-    if affine is not None:
-        raise ValueError("data.affine needs decoded images: it warps the batch's uint8 canvas in the on-device transform, and "
-                         f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
-    if mixup is not None:
-        raise ValueError("data.mixup needs decoded images: it blends the batch's uint8 canvases in the on-device transform, and "
-                         f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
+    for name, given, does in (("mosaic", mosaic, "composes the batch's uint8 images"), ("affine", affine, "warps the batch's uint8 canvas"),
+                              ("mixup", mixup, "blends the batch's uint8 canvases")):
+        if given is not None:
+            raise ValueError(f"data.{name} needs decoded images: it {does} in the on-device transform, and "
+                             f"the synthetic dataset (no parquet at {train_parquet}) yields finished float tensors; remove the key")
     n = 20 if is_test else 256
     train_ds = SyntheticDetectionDataset(max(batch_size, int(n * percent)), res, num_classes, 1234)
     val_ds = SyntheticDetectionDataset(max(batch_size, int(n * percent) // 4), res, num_classes, 4321)

@@ -153,6 +153,54 @@ def mixup_boxes(own, partner, max_boxes):
     return keep_largest(out, out[:, 2] * out[:, 3], max_boxes)
 
 
+def _options(name, given, defaults, train):
+    """What the mosaic, affine and mixup options share: training only, known keys, merged with their defaults."""
+    if not train:
+        raise ValueError(f"{name} is a training augmentation: the validation transform takes none")
+    unknown = set(given) - set(defaults)
+    if unknown:
+        raise ValueError(f"{name}: unknown keys {sorted(unknown)}; expected {sorted(defaults)}")
+    return {**defaults, **given}
+
+
+def _mosaic_options(m):
+    gain = tuple(float(g) for g in m["gain"])
+    if not 0.0 <= m["p"] <= 1.0:
+        raise ValueError(f"mosaic.p must lie in [0, 1], got {m['p']}")
+    if len(gain) != 2 or not 0.0 < gain[0] <= gain[1] <= 2.0:
+        raise ValueError(f"mosaic.gain must be [lo, hi] with 0 < lo <= hi <= 2, got {m['gain']}")
+    if not 0 <= int(m["fill"]) <= 255 or int(m["max_boxes"]) < 1 or int(m["close_epochs"]) < 0:
+        raise ValueError("mosaic: fill is a uint8 level, max_boxes >= 1 and close_epochs >= 0")
+    return dict(p=float(m["p"]), gain=gain, fill=int(m["fill"]), min_box=float(m["min_box"]), min_visible=float(m["min_visible"]),
+                max_boxes=int(m["max_boxes"]), close_epochs=int(m["close_epochs"]))
+
+
+def _affine_options(a, mosaic):
+    if not 0.0 <= a["degrees"] <= 180.0 or not 0.0 <= a["shear"] <= 89.0:
+        raise ValueError(f"affine.degrees must lie in [0, 180] and affine.shear in [0, 89], got {a['degrees']}, {a['shear']}")
+    if not 0.0 <= a["translate"] < 1.0 or not 0.0 <= a["scale"] < 1.0:
+        raise ValueError(f"affine.translate and affine.scale must lie in [0, 1), got {a['translate']}, {a['scale']}")
+    if int(a["fill"]) != a["fill"] or not 0 <= int(a["fill"]) <= 255 or int(a["max_boxes"]) < 1 or int(a["close_epochs"]) < 0:
+        raise ValueError("affine: fill is a uint8 level, max_boxes >= 1 and close_epochs >= 0")
+    if a["min_box"] < 0 or a["min_visible"] < 0 or not a["max_aspect"] > 1:
+        raise ValueError("affine: min_box >= 0, min_visible >= 0 and max_aspect > 1")
+    if mosaic is not None and mosaic["fill"] != int(a["fill"]):
+        raise ValueError(f"affine.fill ({a['fill']}) and mosaic.fill ({mosaic['fill']}) are one level: the launch takes one")
+    return dict(degrees=float(a["degrees"]), translate=float(a["translate"]), scale=float(a["scale"]), shear=float(a["shear"]),
+                fill=int(a["fill"]), min_box=float(a["min_box"]), min_visible=float(a["min_visible"]), max_aspect=float(a["max_aspect"]),
+                max_boxes=int(a["max_boxes"]), close_epochs=int(a["close_epochs"]))
+
+
+def _mixup_options(x):
+    if not 0.0 <= x["p"] <= 1.0:
+        raise ValueError(f"mixup.p must lie in [0, 1], got {x['p']}")
+    if not (x["alpha"] > 0 and math.isfinite(x["alpha"])):
+        raise ValueError(f"mixup.alpha must be positive and finite, got {x['alpha']}")
+    if int(x["max_boxes"]) < 1 or int(x["close_epochs"]) < 0:
+        raise ValueError("mixup: max_boxes >= 1 and close_epochs >= 0")
+    return dict(p=float(x["p"]), alpha=float(x["alpha"]), max_boxes=int(x["max_boxes"]), close_epochs=int(x["close_epochs"]))
+
+
 class BatchTransform:
     """Callable(images, targets) -> (batch on `device`, targets).  images: decoded RGB images as uint8 (H, W, 3) arrays /
     tensors or PIL images; targets: dicts with "boxes" (M, 4) XYWH pixels and "labels" (M, 1) (the reference dataset's
@@ -163,68 +211,12 @@ class BatchTransform:
         self.train, self.size, self.device, self.dtype = train, size, torch.device(device), dtype
         self.flip_p, self.jit = flip_p, (brightness, contrast, saturation, hue)
         self.mean, self.std = mean, std
-        # mosaic: None (off: today's path, call for call) or a dict of MOSAIC_DEFAULTS' keys; `mosaic_on` switches it per
-        # epoch (DevicePreppedLoader.set_epoch turns it off for the last `close_epochs` epochs)
-        self.mosaic = None
-        if mosaic is not None:
-            if not train:
-                raise ValueError("mosaic is a training augmentation: the validation transform takes none")
-            unknown = set(mosaic) - set(MOSAIC_DEFAULTS)
-            if unknown:
-                raise ValueError(f"mosaic: unknown keys {sorted(unknown)}; expected {sorted(MOSAIC_DEFAULTS)}")
-            m = {**MOSAIC_DEFAULTS, **mosaic}
-            gain = tuple(float(g) for g in m["gain"])
-            if not 0.0 <= m["p"] <= 1.0:
-                raise ValueError(f"mosaic.p must lie in [0, 1], got {m['p']}")
-            if len(gain) != 2 or not 0.0 < gain[0] <= gain[1] <= 2.0:
-                raise ValueError(f"mosaic.gain must be [lo, hi] with 0 < lo <= hi <= 2, got {m['gain']}")
-            if not 0 <= int(m["fill"]) <= 255 or int(m["max_boxes"]) < 1 or int(m["close_epochs"]) < 0:
-                raise ValueError("mosaic: fill is a uint8 level, max_boxes >= 1 and close_epochs >= 0")
-            self.mosaic = dict(p=float(m["p"]), gain=gain, fill=int(m["fill"]), min_box=float(m["min_box"]),
-                               min_visible=float(m["min_visible"]), max_boxes=int(m["max_boxes"]),
-                               close_epochs=int(m["close_epochs"]))
-        self.mosaic_on = self.mosaic is not None
-        # affine: None (off: today's path, call for call) or a dict of AFFINE_DEFAULTS' keys; `affine_on` is its per-epoch switch
-        self.affine = None
-        if affine is not None:
-            if not train:
-                raise ValueError("affine is a training augmentation: the validation transform takes none")
-            unknown = set(affine) - set(AFFINE_DEFAULTS)
-            if unknown:
-                raise ValueError(f"affine: unknown keys {sorted(unknown)}; expected {sorted(AFFINE_DEFAULTS)}")
-            a = {**AFFINE_DEFAULTS, **affine}
-            if not 0.0 <= a["degrees"] <= 180.0 or not 0.0 <= a["shear"] <= 89.0:
-                raise ValueError(f"affine.degrees must lie in [0, 180] and affine.shear in [0, 89], got {a['degrees']}, {a['shear']}")
-            if not 0.0 <= a["translate"] < 1.0 or not 0.0 <= a["scale"] < 1.0:
-                raise ValueError(f"affine.translate and affine.scale must lie in [0, 1), got {a['translate']}, {a['scale']}")
-            if int(a["fill"]) != a["fill"] or not 0 <= int(a["fill"]) <= 255 or int(a["max_boxes"]) < 1 or int(a["close_epochs"]) < 0:
-                raise ValueError("affine: fill is a uint8 level, max_boxes >= 1 and close_epochs >= 0")
-            if a["min_box"] < 0 or a["min_visible"] < 0 or not a["max_aspect"] > 1:
-                raise ValueError("affine: min_box >= 0, min_visible >= 0 and max_aspect > 1")
-            if self.mosaic is not None and self.mosaic["fill"] != int(a["fill"]):
-                raise ValueError(f"affine.fill ({a['fill']}) and mosaic.fill ({self.mosaic['fill']}) are one level: the launch takes one")
-            self.affine = dict(degrees=float(a["degrees"]), translate=float(a["translate"]), scale=float(a["scale"]),
-                               shear=float(a["shear"]), fill=int(a["fill"]), min_box=float(a["min_box"]),
-                               min_visible=float(a["min_visible"]), max_aspect=float(a["max_aspect"]),
-                               max_boxes=int(a["max_boxes"]), close_epochs=int(a["close_epochs"]))
-        self.affine_on = self.affine is not None
-        # mixup: None (off: today's path, call for call) or a dict of MIXUP_DEFAULTS' keys; `mixup_on` is its per-epoch switch
-        self.mixup = None
-        if mixup is not None:
-            if not train:
-                raise ValueError("mixup is a training augmentation: the validation transform takes none")
-            unknown = set(mixup) - set(MIXUP_DEFAULTS)
-            if unknown:
-                raise ValueError(f"mixup: unknown keys {sorted(unknown)}; expected {sorted(MIXUP_DEFAULTS)}")
-            x = {**MIXUP_DEFAULTS, **mixup}
-            if not 0.0 <= x["p"] <= 1.0:
-                raise ValueError(f"mixup.p must lie in [0, 1], got {x['p']}")
-            if not (x["alpha"] > 0 and math.isfinite(x["alpha"])):
-                raise ValueError(f"mixup.alpha must be positive and finite, got {x['alpha']}")
-            if int(x["max_boxes"]) < 1 or int(x["close_epochs"]) < 0:
-                raise ValueError("mixup: max_boxes >= 1 and close_epochs >= 0")
-            self.mixup = dict(p=float(x["p"]), alpha=float(x["alpha"]), max_boxes=int(x["max_boxes"]), close_epochs=int(x["close_epochs"]))
-        self.mixup_on = self.mixup is not None
+        # mosaic, affine, mixup: each None (off: the path without the key, call for call) or a dict of its *_DEFAULTS' keys; `*_on`
+        # switches it per epoch (DevicePreppedLoader.set_epoch turns it off for the last `close_epochs` epochs)
+        self.mosaic = None if mosaic is None else _mosaic_options(_options("mosaic", mosaic, MOSAIC_DEFAULTS, train))
+        self.affine = None if affine is None else _affine_options(_options("affine", affine, AFFINE_DEFAULTS, train), self.mosaic)
+        self.mixup = None if mixup is None else _mixup_options(_options("mixup", mixup, MIXUP_DEFAULTS, train))
+        self.mosaic_on, self.affine_on, self.mixup_on = self.mosaic is not None, self.affine is not None, self.mixup is not None
         self._pinned = None                 # reused pinned upload buffer (one memcpy per image into it, one async H2D per batch)
         self._uploaded = None
 
@@ -332,85 +324,92 @@ class BatchTransform:
         geometry record (`mosaic_geometry`'s format); `affine`: per output None (identity), a sample_affine() draw or a
         forward 2 x 3 matrix; `mixup`: per output None (not mixed) or (partner, r) -- all are drawn here when not given."""
         imgs = [self._as_u8(i) for i in images]
+        recs, records, mats, inverse, mix = self._resolve(imgs, params, mosaic, affine, mixup)
+        flat = self._upload(imgs, recs)
+        jitter = self.train and any(len(r[4]) for r in recs)
+        tiles = self._mosaic_tiles(records, recs) if records is not None else None
+        fill = self.affine["fill"] if inverse is not None else self.mosaic["fill"] if tiles is not None else 0
+        tail = (self.size, fill, jitter, self.dtype, self.mean, self.std)
+        if mix is not None:
+            batch = ops.image_prep_mixup(flat, recs, tiles, inverse, [(i, 1.0) if m is None else m for i, m in enumerate(mix)], *tail)
+        elif inverse is not None:
+            batch = ops.image_prep_affine(flat, recs, tiles, inverse, *tail)
+        elif tiles is not None:
+            batch = ops.image_prep_mosaic(flat, recs, tiles, *tail)
+        else:
+            batch = ops.image_prep(flat, recs, self.size, jitter, self.dtype, self.mean, self.std)
+        return batch, None if targets is None else self._boxes(targets, recs, records, mats, mix)
+
+    def _resolve(self, imgs, params, mosaic, affine, mixup):
+        """The decisions of a batch, drawn where not given, in the order sample(), sample_mosaic(), sample_affine(), sample_mixup() ->
+        (PrepImage records, per output None or a mosaic geometry record, forward matrices, their inverse records, mix records); each
+        of the last four is None when that stage does not run (the mix also when nobody mixes: the leaf is then the one a transform
+        without the key takes)."""
+        n = len(imgs)
         params = params if params is not None else [self.sample() for _ in imgs]
-        if mosaic is not None and self.mosaic is None:
-            raise ValueError("mosaic records were passed to a BatchTransform built without mosaic=")
+        for name, given in (("mosaic", mosaic), ("affine", affine), ("mixup", mixup)):
+            if given is not None and getattr(self, name) is None:
+                raise ValueError(f"{name} records were passed to a BatchTransform built without {name}=")
         use_mosaic = self.mosaic is not None and (self.mosaic_on or mosaic is not None)
         if use_mosaic and mosaic is None:
-            mosaic = self.sample_mosaic(len(imgs))
-        if affine is not None and self.affine is None:
-            raise ValueError("affine records were passed to a BatchTransform built without affine=")
-        use_affine = self.affine is not None and (self.affine_on or affine is not None)
-        if use_affine:
-            mats = self._affine_matrices(affine if affine is not None else self.sample_affine(len(imgs)), len(imgs))
+            mosaic = self.sample_mosaic(n)
+        mats = inverse = mix = None
+        if self.affine is not None and (self.affine_on or affine is not None):
+            mats = self._affine_matrices(affine if affine is not None else self.sample_affine(n), n)
             inverse = [affine_record(m) for m in mats]
-        if mixup is not None and self.mixup is None:
-            raise ValueError("mixup records were passed to a BatchTransform built without mixup=")
-        mix = None
         if self.mixup is not None and (self.mixup_on or mixup is not None):
-            mix = self._mix_records(mixup if mixup is not None else self.sample_mixup(len(imgs)), len(imgs))
+            mix = self._mix_records(mixup if mixup is not None else self.sample_mixup(n), n)
             if all(m is None for m in mix):
-                mix = None                      # nobody mixes: the leaf below is the one a transform without the key takes
+                mix = None
         recs, off = [], 0
         for t, (flip, order, fac) in zip(imgs, params):
             h, w = int(t.shape[0]), int(t.shape[1])
             recs.append((off, h, w, flip, order, fac))
             off += h * w * 3
-        if self.device.type == "cuda":
-            if self._pinned is None or self._pinned.numel() < off:
-                self._pinned = torch.empty(int(off * 1.25), dtype=torch.uint8).pin_memory()
-            elif self._uploaded is not None:
-                self._uploaded.synchronize()        # the previous batch's upload has left the buffer
-            for t, r in zip(imgs, recs):
-                self._pinned[r[0]:r[0] + t.numel()].copy_(t.reshape(-1))
-            flat = self._pinned[:off].to(self.device, non_blocking=True)
-            self._uploaded = torch.cuda.Event()
-            self._uploaded.record(torch.cuda.current_stream(self.device))
-        else:
-            flat = torch.cat([t.reshape(-1) for t in imgs])
-        jitter = self.train and any(len(p[1]) for p in params)
-        records = self._mosaic_records(mosaic, recs) if use_mosaic else [None] * len(recs)
-        if mix is not None:
-            fill = self.affine["fill"] if use_affine else self.mosaic["fill"] if use_mosaic else 0
-            batch = ops.image_prep_mixup(flat, recs, self._mosaic_tiles(records, recs) if use_mosaic else None,
-                                         inverse if use_affine else None, [(i, 1.0) if m is None else m for i, m in enumerate(mix)],
-                                         self.size, fill, jitter, self.dtype, self.mean, self.std)
-        elif use_affine:
-            tiles = self._mosaic_tiles(records, recs) if use_mosaic else None
-            batch = ops.image_prep_affine(flat, recs, tiles, inverse, self.size, self.affine["fill"], jitter, self.dtype, self.mean,
-                                          self.std)
-        elif use_mosaic:
-            batch = ops.image_prep_mosaic(flat, recs, self._mosaic_tiles(records, recs), self.size, self.mosaic["fill"], jitter,
-                                          self.dtype, self.mean, self.std)
-        else:
-            batch = ops.image_prep(flat, recs, self.size, jitter, self.dtype, self.mean, self.std)
-        out_t = None
-        if targets is not None:
-            out_t = []
-            sizes = [(r[1], r[2]) for r in recs]
-            for i, (tg, (_, h, w, flip, _, _), rec) in enumerate(zip(targets, recs, records)):
-                new = {k: v for k, v in tg.items() if k not in ("boxes", "labels")}
-                if rec is not None:
-                    m = self.mosaic
-                    new["boxes"] = mosaic_boxes(rec, targets, sizes, self.size, m["min_box"], m["min_visible"], m["max_boxes"])
-                else:
-                    b = tg["boxes"].clone().float().reshape(-1, 4)
-                    if flip:
-                        b[:, 0] = w - (b[:, 0] + b[:, 2])
-                    b[:, [0, 2]] *= self.size / w
-                    b[:, [1, 3]] *= self.size / h
-                    new["boxes"] = torch.cat([b, tg["labels"].float().reshape(-1, 1)], 1)      # dataset_loader.py:76
-                if use_affine:
-                    a = self.affine
-                    new["boxes"] = affine_boxes(mats[i], new["boxes"], self.size, a["min_box"], a["min_visible"], a["max_aspect"],
-                                                a["max_boxes"])
-                out_t.append(new)
-            if mix is not None:                 # the partner's boxes are those of its own unmixed output: read before any is replaced
-                unmixed = [t["boxes"] for t in out_t]
-                for i, m in enumerate(mix):
-                    if m is not None:
-                        out_t[i]["boxes"] = mixup_boxes(unmixed[i], unmixed[m[0]], self.mixup["max_boxes"])
-        return batch, out_t
+        return recs, self._mosaic_records(mosaic, recs) if use_mosaic else None, mats, inverse, mix
+
+    def _upload(self, imgs, recs):
+        """The batch's images back to back on the device: one memcpy per image into the pinned buffer, one async copy per batch."""
+        if self.device.type != "cuda":
+            return torch.cat([t.reshape(-1) for t in imgs])
+        total = sum(t.numel() for t in imgs)
+        if self._pinned is None or self._pinned.numel() < total:
+            self._pinned = torch.empty(int(total * 1.25), dtype=torch.uint8).pin_memory()
+        elif self._uploaded is not None:
+            self._uploaded.synchronize()        # the previous batch's upload has left the buffer
+        for t, r in zip(imgs, recs):
+            self._pinned[r[0]:r[0] + t.numel()].copy_(t.reshape(-1))
+        flat = self._pinned[:total].to(self.device, non_blocking=True)
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record(torch.cuda.current_stream(self.device))
+        return flat
+
+    def _boxes(self, targets, recs, records, mats, mix):
+        """The targets of the outputs: the boxes follow the flip and resize or the mosaic, then the warp, then take the partner's."""
+        out_t = []
+        sizes = [(r[1], r[2]) for r in recs]
+        for i, (tg, (_, h, w, flip, _, _)) in enumerate(zip(targets, recs)):
+            new = {k: v for k, v in tg.items() if k not in ("boxes", "labels")}
+            if records is not None and records[i] is not None:
+                m = self.mosaic
+                new["boxes"] = mosaic_boxes(records[i], targets, sizes, self.size, m["min_box"], m["min_visible"], m["max_boxes"])
+            else:
+                b = tg["boxes"].clone().float().reshape(-1, 4)
+                if flip:
+                    b[:, 0] = w - (b[:, 0] + b[:, 2])
+                b[:, [0, 2]] *= self.size / w
+                b[:, [1, 3]] *= self.size / h
+                new["boxes"] = torch.cat([b, tg["labels"].float().reshape(-1, 1)], 1)      # dataset_loader.py:76
+            if mats is not None:
+                a = self.affine
+                new["boxes"] = affine_boxes(mats[i], new["boxes"], self.size, a["min_box"], a["min_visible"], a["max_aspect"], a["max_boxes"])
+            out_t.append(new)
+        if mix is not None:                 # the partner's boxes are those of its own unmixed output: read before any is replaced
+            unmixed = [t["boxes"] for t in out_t]
+            for i, m in enumerate(mix):
+                if m is not None:
+                    out_t[i]["boxes"] = mixup_boxes(unmixed[i], unmixed[m[0]], self.mixup["max_boxes"])
+        return out_t
 
     def _mosaic_records(self, mosaic, recs):
         """Per output None (plain) or its geometry record, from draws or ready records."""

@@ -753,23 +753,6 @@ def _prep_table_fill(host, recs):
                  *[float(v) for v in fac])
 
 
-def image_prep(src_u8, recs, size, jitter, dtype, mean, std):
-    """Batch of decoded uint8 HWC images (flat device buffer `src_u8`; recs = [(offset, H, W, flip, order[4], factors[4])])
-    -> normalised (N, 3, size, size) tensor of `dtype`: flip + antialiased bilinear resize + colour jitter + normalise
-    (src/data/transforms.py:4-24) in 2 + 2 x (jitter slots) launches for the whole batch."""
-    n = len(recs)
-    rb = lib.query("yolo_prep_image_bytes")
-    host = torch.zeros(n * rb, dtype=torch.uint8).pin_memory()
-    _prep_table_fill(host, recs)
-    table = host.to(src_u8.device, non_blocking=True)
-    stage = torch.empty((n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
-    means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
-    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
-    lib.call("yolo_image_prep", _p(src_u8), _p(table), n, size, int(bool(jitter)), _p(stage), _p(means), _p(out), dt(dtype),
-             *[float(v) for v in mean], *[float(v) for v in std], _stream(src_u8))
-    return out
-
-
 def _tile_table_fill(host_ptr, tiles, limit, who):
     """The MosaicTile records of `tiles` into the (pinned, zeroed) host table at `host_ptr`."""
     for i, (cx, cy, quad) in enumerate(tiles):
@@ -785,27 +768,76 @@ def _tile_table_fill(host_ptr, tiles, limit, who):
                      int(th), int(x0), int(y0), int(cx), int(cy))
 
 
+def _affine_table_fill(host_ptr, affine, who):
+    """The AffineRec records of `affine` into the host table at `host_ptr`."""
+    for i, a in enumerate(affine):
+        if len(a) != 6:
+            raise ValueError(f"{who}: affine record {i} needs six values, got {len(a)}")
+        lib.call("yolo_affine_fill", host_ptr, i, *[float(v) for v in a])
+
+
+def _mix_table_fill(host_ptr, mix, who):
+    """The MixRec records of `mix` into the host table at `host_ptr`."""
+    for i, m in enumerate(mix):
+        if len(m) != 2:
+            raise ValueError(f"{who}: mix record {i} is (partner, r), got {m!r}")
+        lib.call("yolo_mix_fill", host_ptr, i, int(m[0]), float(m[1]), len(mix))
+
+
+def _image_prep_run(who, src_u8, recs, tiles, affine, mix, size, fill, jitter, dtype, mean, std):
+    """The one packer and runner behind image_prep, image_prep_mosaic, image_prep_affine and image_prep_mixup (`who`: the caller's name
+    in messages; tiles, affine, mix: a table or None).  The record sections present travel back to back in one pinned buffer and one
+    upload; one uint8 stage without warp and mix, two with either; the call goes to the narrowest entry point that takes the tables
+    present.  A new stage is one more section here and one more launch in csrc/image_prep.hip::prep_run."""
+    n, dev, st = len(recs), src_u8.device, _stream(src_u8)
+    # (table or None, the query of its bytes per record, records, fill of the host buffer from the section's offset on)
+    sections = [(recs, "yolo_prep_image_bytes", n, lambda h: _prep_table_fill(h, recs)),
+                (tiles, "yolo_mosaic_tile_bytes", 4 * n, lambda h: _tile_table_fill(h.data_ptr(), tiles, src_u8.numel(), who)),
+                (affine, "yolo_affine_bytes", n, lambda h: _affine_table_fill(h.data_ptr(), affine, who)),
+                (mix, "yolo_mix_bytes", n, lambda h: _mix_table_fill(h.data_ptr(), mix, who))]
+    offs, total = [], 0                 # byte offset of each section in the buffer, None = absent
+    for present, size_of, count, _ in sections:
+        offs.append(None if present is None else total)
+        total += 0 if present is None else lib.query(size_of) * count
+    host = torch.zeros(total, dtype=torch.uint8).pin_memory()
+    for (*_, fill_section), off in zip(sections, offs):
+        if off is not None:
+            fill_section(host[off:])
+    table = host.to(dev, non_blocking=True)
+    two = affine is not None or mix is not None
+    stage = torch.empty((2, n, 3, size, size) if two else (n, 3, size, size), dtype=torch.uint8, device=dev)
+    means = torch.empty(4 * n, dtype=torch.float32, device=dev)
+    out = torch.empty((n, 3, size, size), dtype=dtype, device=dev)
+    recs_d, tiles_d, affine_d, mix_d = (0 if off is None else _p(table) + off for off in offs)
+    stages = (_p(stage[0]), _p(stage[1])) if two else (_p(stage),)
+    tail = (int(bool(jitter)), *stages, _p(means), _p(out), dt(dtype), *[float(v) for v in mean], *[float(v) for v in std], st)
+    if mix is not None:
+        lib.call("yolo_image_prep_mixup", _p(src_u8), tiles_d, recs_d, affine_d, mix_d, n, size, int(fill), *tail)
+    elif affine is not None:
+        lib.call("yolo_image_prep_affine", _p(src_u8), tiles_d, recs_d, affine_d, n, size, int(fill), *tail)
+    elif tiles is not None:
+        lib.call("yolo_image_prep_mosaic", _p(src_u8), tiles_d, recs_d, n, size, int(fill), *tail)
+    else:
+        lib.call("yolo_image_prep", _p(src_u8), recs_d, n, size, *tail)
+    return out
+
+
+def image_prep(src_u8, recs, size, jitter, dtype, mean, std):
+    """Batch of decoded uint8 HWC images (flat device buffer `src_u8`; recs = [(offset, H, W, flip, order[4], factors[4])])
+    -> normalised (N, 3, size, size) tensor of `dtype`: flip + antialiased bilinear resize + colour jitter + normalise
+    (src/data/transforms.py:4-24) in 2 + 2 x (jitter slots) launches for the whole batch."""
+    return _image_prep_run("image_prep", src_u8, recs, None, None, None, size, 0, jitter, dtype, mean, std)
+
+
 def image_prep_mosaic(src_u8, recs, tiles, size, fill, jitter, dtype, mean, std):
     """`image_prep` with a mosaic in front of the colour chain.  recs: as for `image_prep`, one per OUTPUT image (its jitter
     order and factors are what is read); tiles: per output (cx, cy, [four of (offset, H, W, flip, tw, th, x0, y0) or None]):
     tile k is that source image resized to (th, tw), placed at (x0, y0) and clipped by quadrant k of the centre (cx, cy); None
     = no tile, the quadrant is `fill`.  Both tables travel in one pinned buffer and one upload."""
-    st = _stream(src_u8)
     n = len(recs)
     if len(tiles) != n:
         raise ValueError(f"image_prep_mosaic: {n} records but {len(tiles)} tile sets")
-    rb, tb = lib.query("yolo_prep_image_bytes"), lib.query("yolo_mosaic_tile_bytes")
-    host = torch.zeros(n * rb + 4 * n * tb, dtype=torch.uint8).pin_memory()
-    _prep_table_fill(host, recs)
-    _tile_table_fill(host.data_ptr() + n * rb, tiles, src_u8.numel(), "image_prep_mosaic")
-    table = host.to(src_u8.device, non_blocking=True)
-    stage = torch.empty((n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
-    means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
-    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
-    lib.call("yolo_image_prep_mosaic", _p(src_u8), _p(table) + n * rb, _p(table), n, size,
-             int(fill), int(bool(jitter)), _p(stage), _p(means), _p(out), dt(dtype), *[float(v) for v in mean],
-             *[float(v) for v in std], st)
-    return out
+    return _image_prep_run("image_prep_mosaic", src_u8, recs, tiles, None, None, size, fill, jitter, dtype, mean, std)
 
 
 def image_prep_affine(src_u8, recs, tiles, affine, size, fill, jitter, dtype, mean, std):
@@ -813,28 +845,10 @@ def image_prep_affine(src_u8, recs, tiles, affine, size, fill, jitter, dtype, me
     the colour chain.  affine: per output the six fp32 values (a00, a01, b0, a10, a11, b1) of the INVERSE map, canvas <-
     output, in continuous pixel coordinates; uncovered pixels are `fill`.  The PrepImage table, the tile table and the affine
     table travel in one pinned buffer and one upload."""
-    st = _stream(src_u8)
     n = len(recs)
     if len(affine) != n or (tiles is not None and len(tiles) != n):
         raise ValueError(f"image_prep_affine: {n} records need {n} affine records and, if any, {n} tile sets")
-    rb, tb, ab = lib.query("yolo_prep_image_bytes"), lib.query("yolo_mosaic_tile_bytes"), lib.query("yolo_affine_bytes")
-    nt = 4 * n * tb if tiles is not None else 0
-    host = torch.zeros(n * rb + nt + n * ab, dtype=torch.uint8).pin_memory()
-    _prep_table_fill(host, recs)
-    if tiles is not None:
-        _tile_table_fill(host.data_ptr() + n * rb, tiles, src_u8.numel(), "image_prep_affine")
-    for i, a in enumerate(affine):
-        if len(a) != 6:
-            raise ValueError(f"image_prep_affine: record {i} needs six values, got {len(a)}")
-        lib.call("yolo_affine_fill", host.data_ptr() + n * rb + nt, i, *[float(v) for v in a])
-    table = host.to(src_u8.device, non_blocking=True)
-    stage = torch.empty((2, n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
-    means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
-    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
-    lib.call("yolo_image_prep_affine", _p(src_u8), _p(table) + n * rb if tiles is not None else 0, _p(table),
-             _p(table) + n * rb + nt, n, size, int(fill), int(bool(jitter)), _p(stage[0]), _p(stage[1]), _p(means), _p(out),
-             dt(dtype), *[float(v) for v in mean], *[float(v) for v in std], st)
-    return out
+    return _image_prep_run("image_prep_affine", src_u8, recs, tiles, affine, None, size, fill, jitter, dtype, mean, std)
 
 
 def image_prep_mixup(src_u8, recs, tiles, affine, mix, size, fill, jitter, dtype, mean, std):
@@ -846,30 +860,7 @@ def image_prep_mixup(src_u8, recs, tiles, affine, mix, size, fill, jitter, dtype
     n = len(recs)
     if len(mix) != n or (tiles is not None and len(tiles) != n) or (affine is not None and len(affine) != n):
         raise ValueError(f"image_prep_mixup: {n} records need {n} mix records and, if any, {n} tile sets and {n} affine records")
-    st = _stream(src_u8)
-    rb, tb, ab, mb = (lib.query(q) for q in ("yolo_prep_image_bytes", "yolo_mosaic_tile_bytes", "yolo_affine_bytes", "yolo_mix_bytes"))
-    nt = 4 * n * tb if tiles is not None else 0
-    na = n * ab if affine is not None else 0
-    host = torch.zeros(n * rb + nt + na + n * mb, dtype=torch.uint8).pin_memory()
-    _prep_table_fill(host, recs)
-    if tiles is not None:
-        _tile_table_fill(host.data_ptr() + n * rb, tiles, src_u8.numel(), "image_prep_mixup")
-    for i, a in enumerate(affine if affine is not None else ()):
-        if len(a) != 6:
-            raise ValueError(f"image_prep_mixup: affine record {i} needs six values, got {len(a)}")
-        lib.call("yolo_affine_fill", host.data_ptr() + n * rb + nt, i, *[float(v) for v in a])
-    for i, m in enumerate(mix):
-        if len(m) != 2:
-            raise ValueError(f"image_prep_mixup: mix record {i} is (partner, r), got {m!r}")
-        lib.call("yolo_mix_fill", host.data_ptr() + n * rb + nt + na, i, int(m[0]), float(m[1]), n)
-    table = host.to(src_u8.device, non_blocking=True)
-    stage = torch.empty((2, n, 3, size, size), dtype=torch.uint8, device=src_u8.device)
-    means = torch.empty(4 * n, dtype=torch.float32, device=src_u8.device)
-    out = torch.empty((n, 3, size, size), dtype=dtype, device=src_u8.device)
-    lib.call("yolo_image_prep_mixup", _p(src_u8), _p(table) + n * rb if tiles is not None else 0, _p(table),
-             _p(table) + n * rb + nt if affine is not None else 0, _p(table) + n * rb + nt + na, n, size, int(fill), int(bool(jitter)),
-             _p(stage[0]), _p(stage[1]), _p(means), _p(out), dt(dtype), *[float(v) for v in mean], *[float(v) for v in std], st)
-    return out
+    return _image_prep_run("image_prep_mixup", src_u8, recs, tiles, affine, mix, size, fill, jitter, dtype, mean, std)
 
 
 def letter_table(recs, size, src_bytes):

@@ -180,3 +180,25 @@ def test_mosaic_fill_exact_and_every_tile_pixel_in_the_set_of_its_own_resize():
         assert is_fill.any() and (got[r][is_fill] == 114).all(), f"record {r}: a fill pixel is not the fill level"
         x, e = si.mosaic_ref_canvas(images, rec, s, 114)
         si.check_levels("mosaic", f"record {r}", got[r], x, e, si.q_resize, si.CAP_RESIZE, canvas)
+
+
+def test_every_route_reproduces_the_recorded_digests():
+    """The four leaves share one runner, so the identity tests between them (identity warp = no warp, r = 1 = unmixed, one-tile mosaic
+    = plain resize) compare that runner with itself.  This holds it to the outputs of the commit named in
+    tests/golden/image_prep_routes.json, recorded on an MI355X by tools/record_prep_digests.py before the routes were merged: all 8
+    combinations of (tiles, affine, mix) through their narrowest leaf, S = 20 (16-byte mixup kernel) and S = 33 (byte kernel), fp32
+    and bf16, jitter off (k_gray_mean's float atomics have no fixed order) -- 32 outputs, byte for byte."""
+    import importlib.util
+    import json
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("record_prep_digests", os.path.join(root, "tools", "record_prep_digests.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(root, "tests", "golden", "image_prep_routes.json")) as f:
+        want = json.load(f)
+    got = tool.digests()
+    assert len(want["digests"]) == 32 and set(got) == set(want["digests"]) and len(set(got.values())) == 32
+    bad = sorted(k for k in got if got[k] != want["digests"][k])
+    print(f"\n[digests] {len(got) - len(bad)} of {len(got)} outputs equal those of commit {want['commit'][:7]}", end="")
+    assert not bad, f"outputs differ from those of commit {want['commit'][:7]}: {bad}"

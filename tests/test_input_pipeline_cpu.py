@@ -99,3 +99,41 @@ def test_parquet_dataset_and_loader_yield_the_collate_format(tmp_path):
     images, targets = next(iter(va))
     # the dataset shuffles its rows like the reference's (`df.sample(frac=...)`, global numpy RNG): either order is right
     assert torch.isfinite(images).all() and sorted(t["name"] for t in targets) == ["im0", "im1"]
+
+
+# a call every one of the four entries would accept: only the named argument of a case below is changed, so the case's refusal is
+# that argument's alone.  The pointers are never read: every case returns before the first launch
+_PREP_BASE = dict(src=0x1000, tiles_dev=0x2000, table_dev=0x3000, affine_dev=0x4000, mix_dev=0x5000, N=3, S=33, fill=114, jitter=0,
+                  stage=0x6000, stage2=0x7000, means=0x8000, out=0x9000, out_dtype=0, m0=0.0, m1=0.0, m2=0.0, s0=1.0, s1=1.0, s2=1.0,
+                  st=None)
+_PREP_REFUSED = {
+    "yolo_image_prep": [dict(N=0), dict(S=0), dict(N=-1), dict(S=-1)],
+    "yolo_image_prep_mosaic": [dict(N=0), dict(S=0), dict(fill=-1), dict(fill=256)],
+    "yolo_image_prep_affine": [dict(N=0), dict(S=0), dict(fill=-1), dict(fill=256), dict(affine_dev=None), dict(stage2=None),
+                               dict(stage2=0x6000)],
+    "yolo_image_prep_mixup": [dict(N=0), dict(S=0), dict(fill=-1), dict(fill=256), dict(mix_dev=None), dict(stage=None),
+                              dict(stage2=None), dict(stage2=0x6000), dict(N=65536)],
+}
+
+
+@pytest.mark.parametrize("entry,change", [(e, c) for e, cases in _PREP_REFUSED.items() for c in cases],
+                         ids=[f"{e[5:]}-{k}={v}" for e, cases in _PREP_REFUSED.items() for c in cases for k, v in c.items()])
+def test_the_four_image_prep_entries_refuse_bad_arguments_before_any_launch(entry, change):
+    """Each entry keeps its own refusals (YOLO_ERR_ARG = 1001): N, S < 1 everywhere; a fill outside a uint8 level where the entry
+    has one; the warp entry its table and a second stage that is another buffer; the mixup entry those of its own and N > 65535."""
+    from src.hipops import lib
+    lib.load()
+    names = lib._protos[entry][2]
+    assert set(change) <= set(names), (entry, change)
+    assert lib.query(entry, *[{**_PREP_BASE, **change}[a] for a in names]) == 1001, (entry, change)
+
+
+def test_yolo_image_prep_has_no_fill_to_refuse():
+    """The plain entry takes no fill level at all (its canvas has no uncovered pixel), so a level such as 999 is never seen by it, and
+    an affine table, a mix table or a second stage are not its arguments either.  No device here: it is called with N = 0 alone and
+    answers for that."""
+    from src.hipops import lib
+    lib.load()
+    names = lib._protos["yolo_image_prep"][2]
+    assert not {"fill", "tiles_dev", "affine_dev", "mix_dev", "stage2"} & set(names)
+    assert lib.query("yolo_image_prep", *[{**_PREP_BASE, "fill": 999, "N": 0}[a] for a in names]) == 1001
