@@ -10,7 +10,8 @@ transpose, bucket and weight-pack leaves are held to tests/strict_move.py in tes
 exactly, slices with their neighbours), their cases here stay as the anchor; head decode, DFL, NMS and the validation
 kernels (csrc/decode_nms.hip) are held to tests/strict_post.py in tests/test_gpu_post.py (decode inside a derived bound, NMS
 rows and validation counters bit for bit against the oracle at every structural edge), the decode and NMS tests here stay
-(the reference's goldens and the config-5 tensor).  check():
+(the reference's goldens and the config-5 tensor).  All of this is finite data: exact NaN / Inf propagation of the convolutions,
+BatchNorm and attention is held by tests/strict_nonfinite.py in tests/test_gpu_nonfinite.py.  check():
 tolerances: fp32 kernels 1e-4 relative to the tensor's max magnitude; bf16/f16 kernels accumulate in fp32
 and round once, the stand-in does the same from the same rounded inputs, so 2 output ulps
 (bf16: 2^-7, f16: 2^-10 relative) of the tensor's max magnitude.  Integer outputs (pool argmax,
