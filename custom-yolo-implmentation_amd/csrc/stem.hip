@@ -72,6 +72,112 @@ __global__ void k_stem_unpack_dw(const float* __restrict__ dw32, int Cout, P* __
 constexpr int STEM_SEG = 128;
 constexpr int STEM_ROWW = 2 * STEM_SEG + 1;
 constexpr int STEM_IR = 5;          // input rows per channel for TWO output rows (the middle one is shared)
+constexpr int STEM_ROWS = 3 * STEM_IR;
+constexpr int STEM_C0 = 3;          // staged column of image column 2*ow0 - 1: a 16-byte packet starts at [..][4]
+typedef float StemRow[STEM_ROWW + 7];
+
+// ---- the tile of the three kernels below, once ---------------------------------------------------------------------------
+// Linear tile index -> (image, first of two output rows, first of 128 output pixels); the segment runs fastest.
+struct StemTile {
+    int n, oh0, ow0;
+    __host__ __device__ constexpr int iw0() const { return 2 * ow0 - 1; }     // image column of staged column STEM_C0
+};
+__host__ __device__ constexpr int stem_segs(int OW) { return (OW + STEM_SEG - 1) / STEM_SEG; }
+__host__ __device__ constexpr int stem_ohp(int OH) { return (OH + 1) >> 1; }
+template <typename I>               // I: the index type the caller divides in (the forward's block index is 32-bit)
+__host__ __device__ constexpr StemTile stem_tile(I tl, int segs, int ohp) {
+    return StemTile{(int)(tl / segs / ohp), (int)(tl / segs % ohp) * 2, (int)(tl % segs) * STEM_SEG};
+}
+constexpr long stem_tiles(int N, int OH, int OW) { return (long)N * stem_ohp(OH) * stem_segs(OW); }
+static_assert(stem_tile((2L * 10 + 7) * 3 + 2, 3, 10).n == 2 && stem_tile(83L, 3, 10).oh0 == 14 && stem_tile(83u, 3, 10).ow0 == 256 &&
+              stem_tile(83, 3, 10).iw0() == 511 && stem_tiles(9, 232, 4) == 1044, "tile decode");
+
+constexpr bool stem_shape_ok(int H, int W, int OH, int OW) { return OH == (H - 1) / 2 + 1 && OW == (W - 1) / 2 + 1; }
+
+// The channel-tile counts CT = Cout / 16 the three kernels are instantiated for, once: STEM_DISPATCH_CT runs its statement with CT a
+// constant (any other count: YOLO_ERR_ARG, as YOLO_DISPATCH_T does for a dtype), stem_ct_ok is yolo_stem_conv_eligible's table.
+#define STEM_CTS(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
+#define STEM_CT_CASE(N, ...) case N: { constexpr int CT = N; __VA_ARGS__; } break;
+#define STEM_DISPATCH_CT(ct, ...) switch (ct) { STEM_CTS(STEM_CT_CASE, __VA_ARGS__) default: return YOLO_ERR_ARG; }
+#define STEM_CT_IS(N, ct) || (ct) == N
+constexpr bool stem_ct_ok(int ct) { return false STEM_CTS(STEM_CT_IS, ct); }
+static_assert(stem_ct_ok(1) && stem_ct_ok(6) && stem_ct_ok(8) && !stem_ct_ok(0) && !stem_ct_ok(5) && !stem_ct_ok(7) && !stem_ct_ok(9), "CT list");
+
+// Unfold column k = ci*9 + kh*3 + kw -> row of the 3 x 5 staged window (for output row j of the pair add 2*j) and column offset
+// (pixel p reads staged column STEM_C0 + 2*p + col); k >= 27 is the zero padding of K to 32 and reads nothing: row < 0.
+struct StemTap { int row, col; };
+__host__ __device__ constexpr StemTap stem_tap(int k) {
+    const int ci = k / 9, r3 = k / 3;                    // kh = r3 - ci*3, kw = k - r3*3: two divisions, the forward decodes 8 taps per pixel
+    return StemTap{k < 27 ? ci * STEM_IR + (r3 - ci * 3) : -1, k - r3 * 3};
+}
+constexpr bool stem_tap_is(int k, int ci, int kh, int kw) { return stem_tap(k).row == ci * STEM_IR + kh && stem_tap(k).col == kw; }
+static_assert(stem_tap_is(0, 0, 0, 0) && stem_tap_is(5, 5 / 9, 5 / 3 % 3, 5 % 3) && stem_tap_is(13, 1, 1, 1) && stem_tap_is(17, 1, 2, 2) &&
+              stem_tap_is(26, 26 / 9, 26 / 3 % 3, 26 % 3) && stem_tap_is(26, 2, 2, 2) && stem_tap(27).row < 0 && stem_tap(31).row < 0, "tap map");
+
+// Image-row stager.  rows[ci*5 + ir][STEM_C0 + c] = image (n, ci), row 2*oh0 - 1 + ir, column iw0 + c for c in [0, 257).  Contract:
+//  * every thread of the workgroup calls it; the barrier before it (the previous tile's readers are done) and the one after it
+//    (the rows are published) are the caller's;
+//  * a row above or below the image and a column at or past W hold 0 -- the conv's padding; the zero is SELECTED, never a product,
+//    so a NaN / Inf outside the window does not enter (tests/test_gpu_nonfinite.py); the address of such an element is clamped to
+//    row 0 / column 2*ow0, which exist, and there is no branch between the loads;
+//  * the left-edge column iw0 is read from the image only when ow0 > 0 (for ow0 = 0 it is the padding column -1: zero, no read);
+//  * W % 4 == 0: one 16-byte load per lane = one row segment per wave instruction (a lane's four columns exist together or not
+//    at all), a wave's (up to four) row segments are ALL in flight before the first LDS store; any other W: the scalar path.
+// The forward calls it.  k_stem_wgrad and k_stem_bn_wgrad carry the same text in their tile loops under the same contract (the second
+// with its dz arithmetic between the halves): called from there it cost 0.4 % of either kernel.  Change all three together.
+constexpr int STEM_RPW = (STEM_ROWS + 3) / 4;
+struct StemRowRegs { float4 v[STEM_RPW]; float edge[STEM_RPW]; };
+
+__device__ __forceinline__ void stem_rows_load(StemRowRegs& s, const float* __restrict__ img, const StemTile t, int H, int W,
+                                               int lane, int wave) {
+    const int c = lane * 4;
+#pragma unroll
+    for (int k = 0; k < STEM_RPW; ++k) {
+        const int r = wave + 4 * k, rr = r < STEM_ROWS ? r : 0;
+        const int ci = rr / STEM_IR, ir = rr - ci * STEM_IR;
+        const int ih = 2 * t.oh0 + ir - 1;
+        const bool rok = ih >= 0 && ih < H;
+        const float* src = img + (((long)t.n * 3 + ci) * H + (rok ? ih : 0)) * (long)W + 2 * t.ow0;
+        const bool cok = 2 * t.ow0 + c < W;                                             // W % 4 == 0: all four or none
+        s.v[k] = *reinterpret_cast<const float4*>(src + (cok ? c : 0));
+        if (!(rok && cok)) s.v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        s.edge[k] = (lane == 0 && t.ow0 > 0) ? src[-1] : 0.f;
+        if (!rok) s.edge[k] = 0.f;
+    }
+}
+
+__device__ __forceinline__ void stem_rows_store(StemRow* rows, const StemRowRegs& s, int lane, int wave) {
+    const int c = lane * 4;
+#pragma unroll
+    for (int k = 0; k < STEM_RPW; ++k) {
+        const int r = wave + 4 * k;
+        if (r < STEM_ROWS) {
+            *reinterpret_cast<float4*>(&rows[r][STEM_C0 + 1 + c]) = s.v[k];
+            if (lane == 0) rows[r][STEM_C0] = s.edge[k];
+        }
+    }
+}
+
+__device__ __forceinline__ void stem_rows_scalar(StemRow* rows, const float* __restrict__ img, const StemTile t, int H, int W, int tid) {
+    for (int idx = tid; idx < STEM_ROWS * STEM_ROWW; idx += 256) {
+        const int r = idx / STEM_ROWW, c = idx - r * STEM_ROWW;
+        const int ci = r / STEM_IR, ir = r - ci * STEM_IR;
+        const int ih = 2 * t.oh0 + ir - 1, iw = t.iw0() + c;
+        const bool ok = ih >= 0 && ih < H && iw >= 0 && iw < W;
+        rows[r][STEM_C0 + c] = ok ? img[(((long)t.n * 3 + ci) * H + ih) * (long)W + iw] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void stem_stage_rows(StemRow* rows, const float* __restrict__ img, const StemTile t, int H, int W, int tid,
+                                                int lane, int wave) {
+    if ((W & 3) == 0) {
+        StemRowRegs s;
+        stem_rows_load(s, img, t, H, W, lane, wave);
+        stem_rows_store(rows, s, lane, wave);
+    } else {
+        stem_rows_scalar(rows, img, t, H, W, tid);
+    }
+}
 
 template <typename T, int CT>
 __global__ __launch_bounds__(256) void k_stem_conv(const float* __restrict__ img, const T* __restrict__ wp,
@@ -79,52 +185,12 @@ __global__ __launch_bounds__(256) void k_stem_conv(const float* __restrict__ img
                                                    int W, int OH, int OW, int Cout, const float* __restrict__ bias, int act) {
     typedef mfma_ops<T> ops;
     typedef typename ops::frag frag;
-    // rows[ci*5 + ir][4 + c] = input row 2*oh0 - 1 + ir, column 2*ow0 + c (c in [0, 256)); [..][3] = column 2*ow0 - 1
-    __shared__ __attribute__((aligned(16))) float rows[3 * STEM_IR][STEM_ROWW + 7];
+    __shared__ __attribute__((aligned(16))) StemRow rows[STEM_ROWS];
     __shared__ float sacc[2][16 * CT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, kg = lane >> 4;
-    const int segs = (OW + STEM_SEG - 1) / STEM_SEG, ohp = (OH + 1) >> 1;
-    const int seg = blockIdx.x % segs;
-    const int t = blockIdx.x / segs;
-    const int oh0 = (t % ohp) * 2, n = t / ohp;
-    const int ow0 = seg * STEM_SEG, iw0 = 2 * ow0 - 1;
-    if ((W & 3) == 0) {
-        // one 16-byte load per lane = one whole row segment per wave instruction
-        // a wave's (up to four) row segments: all loads in flight before the first LDS store (clamped addresses, no branch)
-        constexpr int RPW = (3 * STEM_IR + 3) / 4;
-        float4 v[RPW];
-        float edge[RPW];
-        const int c = lane * 4;
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {
-            const int r = wave + 4 * k, rr = r < 3 * STEM_IR ? r : 0;
-            const int ci = rr / STEM_IR, ir = rr - ci * STEM_IR;
-            const int ih = 2 * oh0 + ir - 1;
-            const bool rok = ih >= 0 && ih < H;
-            const float* src = img + (((long)n * 3 + ci) * H + (rok ? ih : 0)) * (long)W + 2 * ow0;
-            const bool cok = 2 * ow0 + c < W;                                               // W % 4 == 0: all four or none
-            v[k] = *reinterpret_cast<const float4*>(src + (cok ? c : 0));
-            if (!(rok && cok)) v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            edge[k] = (lane == 0 && ow0 > 0) ? src[-1] : 0.f;
-            if (!rok) edge[k] = 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {
-            const int r = wave + 4 * k;
-            if (r < 3 * STEM_IR) {
-                *reinterpret_cast<float4*>(&rows[r][4 + c]) = v[k];
-                if (lane == 0) rows[r][3] = edge[k];
-            }
-        }
-    } else {
-        for (int idx = tid; idx < 3 * STEM_IR * STEM_ROWW; idx += 256) {
-            const int r = idx / STEM_ROWW, c = idx - r * STEM_ROWW;
-            const int ci = r / STEM_IR, ir = r - ci * STEM_IR;
-            const int ih = 2 * oh0 + ir - 1, iw = iw0 + c;
-            const bool ok = ih >= 0 && ih < H && iw >= 0 && iw < W;
-            rows[r][3 + c] = ok ? img[(((long)n * 3 + ci) * H + ih) * (long)W + iw] : 0.f;
-        }
-    }
+    const StemTile t = stem_tile(blockIdx.x, stem_segs(OW), stem_ohp(OH));
+    const int n = t.n, oh0 = t.oh0, ow0 = t.ow0;
+    stem_stage_rows(rows, img, t, H, W, tid, lane, wave);
     stats_zero(&sacc[0][0], 2 * 16 * CT, tid, 256);         // before the barrier that publishes the rows: the statistics need no extra one
     frag a[CT];
 #pragma unroll
@@ -141,9 +207,8 @@ __global__ __launch_bounds__(256) void k_stem_conv(const float* __restrict__ img
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int k = kg * 8 + e;
-            const int ci = k / 9, r3 = k / 3, kh = r3 - ci * 3, kw = k - r3 * 3;
-            v[e] = (k < 27 && live[i]) ? rows[k < 27 ? ci * STEM_IR + 2 * j + kh : 0][2 * p + kw + 3] : 0.f;
+            const StemTap tap = stem_tap(kg * 8 + e);
+            v[e] = (tap.row >= 0 && live[i]) ? rows[tap.row >= 0 ? tap.row + 2 * j : 0][2 * p + tap.col + STEM_C0] : 0.f;
         }
         frag b;
 #pragma unroll
@@ -201,39 +266,77 @@ __device__ __forceinline__ typename mfma_ops<T>::frag stem_tr_frag(const T* p_lo
 
 constexpr int stem_ldy(int ct) { return ct == 4 ? 72 : ct == 8 ? 144 : ct * 16 + (ct == 2 ? 0 : 8); }
 
+// Unfold fragments of a pixel run, for the two kernels whose reduction index is the pixel: fb[nt][e] = unfold column tap[nt] (the lane's
+// k = nt*16 + i16) of output pixel px + e of output row j of the pair, e = 0..7, from the staged rows, rounded to T exactly as the column
+// tensor was.  G3: g3[nt] += the rounded values of the run's first `nlive` pixels, the ones that exist (a pixel past the row / image
+// end still has taps inside the image); without G3 nothing of it is compiled.
+template <typename T, bool G3>
+__device__ __forceinline__ void stem_gather_run(typename mfma_ops<T>::frag (&fb)[2], const StemRow* rows, const StemTap (&tap)[2], int j,
+                                                int px, float* g3 = nullptr, bool rowok = false, int ow = 0, int OW = 0) {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float x = tap[nt].row >= 0 ? rows[tap[nt].row < 0 ? 0 : tap[nt].row + 2 * j][2 * (px + e) + tap[nt].col + STEM_C0] : 0.f;
+            const T xr = from_f<T>(x);
+            fb[nt][e] = xr;
+            if constexpr (G3) g3[nt] += (rowok && ow + e < OW) ? to_f<T>(xr) : 0.f;
+        }
+    }
+}
+
+// The four waves add their MFMA sums one after the other: wave 0 stores, waves 1, 2, 3 add, one barrier in front of each turn (fixed
+// order: the result does not depend on the schedule).  a0 goes to the matrix [16*CT][32] at sum, and with NM = 2 a1 to the one behind it
+// (NM = 1: a1 is not read): D rows = co (ct*16 + g*4 + r), cols = k (nt*16 + i16).  Two matrices share the turns, so a second one
+// costs no barrier; also(first) runs inside the wave's turn too: the caller's other sums.  The barrier that publishes the last turn
+// is the caller's.  The accumulators are two arrays, not acc[2][CT][2]: as one array k_stem_bn_wgrad took 4 more registers.
+template <int NM, int CT, typename F>
+__device__ __forceinline__ void stem_wave_combine(float* sum, const f32x4 (&a0)[CT][2], const f32x4 (&a1)[CT][2], int wave, int g, int i16,
+                                                  F also) {
+    for (int wv = 0; wv < 4; ++wv) {
+        __syncthreads();
+        if (wave == wv) {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float* e = &sum[(ct * 16 + g * 4 + r) * 32 + nt * 16 + i16];
+                        e[0] = wv == 0 ? a0[ct][nt][r] : e[0] + a0[ct][nt][r];
+                        if constexpr (NM == 2) e[CT * 512] = wv == 0 ? a1[ct][nt][r] : e[CT * 512] + a1[ct][nt][r];
+                    }
+            also(wv == 0);
+        }
+    }
+}
+
 template <typename T, int CT>
 __global__ __launch_bounds__(256) void k_stem_wgrad(const float* __restrict__ img, const T* __restrict__ dy, int ldy,
                                                     float* __restrict__ part, int N, int H, int W, int OH, int OW, long tiles) {
     typedef mfma_ops<T> ops;
     typedef typename ops::frag frag;
     constexpr int LDY = stem_ldy(CT), COUT = 16 * CT;
-    __shared__ __attribute__((aligned(16))) float rows[3 * STEM_IR][STEM_ROWW + 7];
+    __shared__ __attribute__((aligned(16))) StemRow rows[STEM_ROWS];
     __shared__ __attribute__((aligned(16))) T ys[2 * STEM_SEG * LDY];
     __shared__ float sum[COUT * 32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, c4 = 4 * (i16 & 3);
-    const int segs = (OW + STEM_SEG - 1) / STEM_SEG, ohp = (OH + 1) >> 1;
+    const int segs = stem_segs(OW), ohp = stem_ohp(OH);
     f32x4 acc[CT][2];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) acc[ct][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // this lane's two unfold columns: k = nt*16 + i16 -> (ci, kh, kw); k >= 27 reads nothing
-    int krow[2], kcol[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const int k = nt * 16 + i16, ci = k / 9, r3 = k / 3;
-        krow[nt] = k < 27 ? ci * STEM_IR + (r3 - ci * 3) : -1;
-        kcol[nt] = k - r3 * 3 + 3;
-    }
+    const StemTap tap[2] = {stem_tap(i16), stem_tap(16 + i16)};       // this lane's two unfold columns: k = nt*16 + i16
     for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
-        const int seg = (int)(tl % segs);
-        const long t = tl / segs;
-        const int oh0 = (int)(t % ohp) * 2, n = (int)(t / ohp);
-        const int ow0 = seg * STEM_SEG, iw0 = 2 * ow0 - 1;
+        const StemTile t = stem_tile(tl, segs, ohp);
+        const int n = t.n, oh0 = t.oh0, ow0 = t.ow0;
         __syncthreads();                                    // the previous tile's fragments have been read
+        // the row stager's text (contract: at stem_rows_load), not a call: as a call this loop measured 0.4 % slower
+        const int iw0 = t.iw0();
         if ((W & 3) == 0) {
-            constexpr int RPW = (3 * STEM_IR + 3) / 4;            // a wave's row segments: all loads before the first LDS store
+            constexpr int RPW = STEM_RPW;
             float4 v[RPW];
             float edge[RPW];
             const int c = lane * 4;
@@ -291,39 +394,17 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const float* __restrict__ im
         for (int j = 0; j < 2; ++j) {                       // wave w: the 32-pixel group w of both output rows
             const int px0 = wave * 32;
             frag fb[2];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float v = krow[nt] >= 0 ? rows[krow[nt] < 0 ? 0 : krow[nt] + 2 * j][2 * (px0 + 8 * g + e) + kcol[nt]] : 0.f;
-                    fb[nt][e] = from_f<T>(v);
-                }
-            }
+            stem_gather_run<T, false>(fb, rows, tap, j, px0 + 8 * g);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                const T* p = ys + (j * STEM_SEG + px0 + 8 * g + q) * LDY + ct * 16 + c4;
+                const T* p = ys +(j * STEM_SEG + px0 + 8 * g + q) * LDY + ct * 16 + c4;
                 const frag fa = stem_tr_frag<T>(p, p + 4 * LDY);
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) acc[ct][nt] = ops::mma(fa, fb[nt], acc[ct][nt]);
             }
         }
     }
-    // D rows = co (ct*16 + g*4 + r), cols = k (nt*16 + i16)
-    // the four waves add their sums one after the other (fixed order: the result does not depend on the schedule)
-    for (int wv = 0; wv < 4; ++wv) {
-        __syncthreads();
-        if (wave == wv) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float* e = &sum[(ct * 16 + g * 4 + r) * 32 + nt * 16 + i16];
-                        *e = wv == 0 ? acc[ct][nt][r] : *e + acc[ct][nt][r];
-                    }
-        }
-    }
+    stem_wave_combine<1>(sum, acc, acc, wave, g, i16, [](bool) {});
     __syncthreads();
     float* o = part + (long)blockIdx.x * COUT * 32;
     for (int c = tid; c < COUT * 32; c += 256) o[c] = sum[c];
@@ -347,21 +428,12 @@ constexpr int STEM_WG_SLABS = 1024;
 template <typename T>
 int launch_stem_wgrad(const float* img, const void* dy, int ldy, float* part, int N, int H, int W, int OH, int OW, int Cout,
                       int* nslab, hipStream_t st) {
-    const long tiles = (long)N * ((OH + 1) / 2) * ((OW + STEM_SEG - 1) / STEM_SEG);
+    const long tiles = stem_tiles(N, OH, OW);
     if (tiles <= 0) return YOLO_ERR_ARG;
     const int grid = (int)(tiles < STEM_WG_SLABS ? tiles : STEM_WG_SLABS);
     *nslab = grid;
-#define STEM_WG(CT) hipLaunchKernelGGL((k_stem_wgrad<T, CT>), dim3(grid), dim3(256), 0, st, img, (const T*)dy, ldy, part, N, H, W, OH, OW, tiles)
-    switch (Cout / 16) {
-        case 1: STEM_WG(1); break;
-        case 2: STEM_WG(2); break;
-        case 3: STEM_WG(3); break;
-        case 4: STEM_WG(4); break;
-        case 6: STEM_WG(6); break;
-        case 8: STEM_WG(8); break;
-        default: return YOLO_ERR_ARG;
-    }
-#undef STEM_WG
+    STEM_DISPATCH_CT(Cout / 16, hipLaunchKernelGGL((k_stem_wgrad<T, CT>), dim3(grid), dim3(256), 0, st, img, (const T*)dy, ldy, part, N, H,
+                                                   W, OH, OW, tiles));
     return YOLO_LAUNCH_CHECK();
 }
 
@@ -393,11 +465,11 @@ __global__ __launch_bounds__(256) void k_stem_bn_wgrad(const float* __restrict__
     constexpr int CPP = COUT / 8, PPT = 256 / CPP, NP = (2 * STEM_SEG + PPT - 1) / PPT;
     constexpr int RED = 17;                                  // row stride of the channel-sum exchange (16 values per thread)
     static_assert((2 * COUT * 32 + 32 + 256 * RED) * sizeof(float) <= 2 * TILE * sizeof(T), "the sums reuse the two tiles");
-    __shared__ __attribute__((aligned(16))) float rows[3 * STEM_IR][STEM_ROWW + 7];
+    __shared__ __attribute__((aligned(16))) StemRow rows[STEM_ROWS];
     __shared__ __attribute__((aligned(16))) T zs[2 * TILE];      // [0, TILE): dz rounded to T; [TILE, 2 TILE): y as stored
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, c4 = 4 * (i16 & 3);
-    const int segs = (OW + STEM_SEG - 1) / STEM_SEG, ohp = (OH + 1) >> 1;
+    const int segs = stem_segs(OW), ohp = stem_ohp(OH);
     const int cpc = tid % CPP, pl = tid / CPP;
     const bool mine = pl < PPT;                              // Cout = 48, 96: four threads hold no chunk
     f32x4 acc1[CT][2], acc2[CT][2];
@@ -412,19 +484,12 @@ __global__ __launch_bounds__(256) void k_stem_bn_wgrad(const float* __restrict__
         sc[j] = scale[cpc * 8 + j];
         sh[j] = shift[cpc * 8 + j];
     }
-    int krow[2], kcol[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const int k = nt * 16 + i16, ci = k / 9, r3 = k / 3;
-        krow[nt] = k < 27 ? ci * STEM_IR + (r3 - ci * 3) : -1;
-        kcol[nt] = k - r3 * 3 + 3;
-    }
+    const StemTap tap[2] = {stem_tap(i16), stem_tap(16 + i16)};       // this lane's two unfold columns: k = nt*16 + i16
     // dout and y of tile tl: 16-byte chunks, pixels past the row / image end are zeros (clamped addresses, no branch)
     chunk dv[NP], yv[NP];
     auto fetch = [&](long tl) {
-        const int seg = (int)(tl % segs);
-        const long t = tl / segs;
-        const int oh0 = (int)(t % ohp) * 2, n = (int)(t / ohp), ow0 = seg * STEM_SEG;
+        const StemTile t = stem_tile(tl, segs, ohp);
+        const int n = t.n, oh0 = t.oh0, ow0 = t.ow0;
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const int px = pl + k * PPT, j = px / STEM_SEG, p = px - j * STEM_SEG;
@@ -437,12 +502,12 @@ __global__ __launch_bounds__(256) void k_stem_bn_wgrad(const float* __restrict__
     };
     if (blockIdx.x < tiles) fetch(blockIdx.x);
     for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
-        const int seg = (int)(tl % segs);
-        const long t = tl / segs;
-        const int oh0 = (int)(t % ohp) * 2, n = (int)(t / ohp);
-        const int ow0 = seg * STEM_SEG, iw0 = 2 * ow0 - 1;
+        const StemTile t = stem_tile(tl, segs, ohp);
+        const int oh0 = t.oh0, ow0 = t.ow0;
         __syncthreads();                                    // the previous tile's fragments have been read
-        constexpr int RPW = (3 * STEM_IR + 3) / 4;            // a wave's image row segments: in flight during the dz arithmetic
+        // the row stager's two halves as text, as in k_stem_wgrad: a wave's image row segments are in flight during the dz arithmetic
+        const int n = t.n;
+        constexpr int RPW = STEM_RPW;
         float4 v[RPW];
         float edge[RPW];
         const bool w4 = (W & 3) == 0;
@@ -491,32 +556,15 @@ __global__ __launch_bounds__(256) void k_stem_bn_wgrad(const float* __restrict__
                     if (lane == 0) rows[r][3] = edge[k];
                 }
             }
-        } else {
-            for (int idx = tid; idx < 3 * STEM_IR * STEM_ROWW; idx += 256) {
-                const int r = idx / STEM_ROWW, c = idx - r * STEM_ROWW;
-                const int ci = r / STEM_IR, ir = r - ci * STEM_IR;
-                const int ih = 2 * oh0 + ir - 1, iw = iw0 + c;
-                const bool ok = ih >= 0 && ih < H && iw >= 0 && iw < W;
-                rows[r][3 + c] = ok ? img[(((long)n * 3 + ci) * H + ih) * (long)W + iw] : 0.f;
-            }
         }
+        else stem_rows_scalar(rows, img, t, H, W, tid);
         if (tl + gridDim.x < tiles) fetch(tl + gridDim.x);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 2; ++j) {                       // wave w: the 32-pixel group w of both output rows
             const int px0 = wave * 32;
-            const bool rowok = oh0 + j < OH;
             frag fb[2];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float x = krow[nt] >= 0 ? rows[krow[nt] < 0 ? 0 : krow[nt] + 2 * j][2 * (px0 + 8 * g + e) + kcol[nt]] : 0.f;
-                    const T xr = from_f<T>(x);
-                    fb[nt][e] = xr;
-                    g3[nt] += (rowok && ow0 + px0 + 8 * g + e < OW) ? to_f<T>(xr) : 0.f;
-                }
-            }
+            stem_gather_run<T, true>(fb, rows, tap, j, px0 + 8 * g, g3, oh0 + j < OH, ow0 + px0 + 8 * g, OW);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
                 const T* p = zs + (j * STEM_SEG + px0 + 8 * g + q4) * LDY + ct * 16 + c4;
@@ -539,27 +587,12 @@ __global__ __launch_bounds__(256) void k_stem_bn_wgrad(const float* __restrict__
         g3[nt] += __shfl_xor(g3[nt], 16, 64);
         g3[nt] += __shfl_xor(g3[nt], 32, 64);
     }
-    // D rows = co (ct*16 + g*4 + r), cols = k (nt*16 + i16)
-    // the four waves add their sums one after the other (fixed order: the result does not depend on the schedule)
-    for (int wv = 0; wv < 4; ++wv) {
-        __syncthreads();
-        if (wave == wv) {
+    stem_wave_combine<2>(sum, acc1, acc2, wave, g, i16, [&](bool first) {       // G3 takes the same turns
+        if (g == 0) {
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float* e = &sum[(ct * 16 + g * 4 + r) * 32 + nt * 16 + i16];
-                        e[0] = wv == 0 ? acc1[ct][nt][r] : e[0] + acc1[ct][nt][r];
-                        e[COUT * 32] = wv == 0 ? acc2[ct][nt][r] : e[COUT * 32] + acc2[ct][nt][r];
-                    }
-            if (g == 0) {
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) g3s[nt * 16 + i16] = wv == 0 ? g3[nt] : g3s[nt * 16 + i16] + g3[nt];
-            }
+            for (int nt = 0; nt < 2; ++nt) g3s[nt * 16 + i16] = first ? g3[nt] : g3s[nt * 16 + i16] + g3[nt];
         }
-    }
+    });
 #pragma unroll
     for (int j = 0; j < 8; ++j) { red[tid * RED + j] = s[j]; red[tid * RED + 8 + j] = q[j]; }
     __syncthreads();
@@ -614,40 +647,22 @@ __global__ __launch_bounds__(1024) void k_stem_bn_wgrad_finalize(const float* __
 template <typename T, int ACT>
 int launch_stem_bn_wgrad(const float* img, const void* dout, int ldd, const void* y, int ldy, const float* scale,
                          const float* shift, float* part, int N, int H, int W, int OH, int OW, int Cout, int* nslab, hipStream_t st) {
-    const long tiles = (long)N * ((OH + 1) / 2) * ((OW + STEM_SEG - 1) / STEM_SEG);
+    const long tiles = stem_tiles(N, OH, OW);
     if (tiles <= 0) return YOLO_ERR_ARG;
     const int grid = (int)(tiles < STEM_BN_SLABS ? tiles : STEM_BN_SLABS);
     *nslab = grid;
-#define STEM_BW(CT) hipLaunchKernelGGL((k_stem_bn_wgrad<T, CT, ACT>), dim3(grid), dim3(256), 0, st, img, (const T*)dout, ldd, (const T*)y, ldy, scale, shift, part, N, H, W, OH, OW, tiles)
-    switch (Cout / 16) {
-        case 1: STEM_BW(1); break;
-        case 2: STEM_BW(2); break;
-        case 3: STEM_BW(3); break;
-        case 4: STEM_BW(4); break;
-        case 6: STEM_BW(6); break;
-        case 8: STEM_BW(8); break;
-        default: return YOLO_ERR_ARG;
-    }
-#undef STEM_BW
+    STEM_DISPATCH_CT(Cout / 16, hipLaunchKernelGGL((k_stem_bn_wgrad<T, CT, ACT>), dim3(grid), dim3(256), 0, st, img, (const T*)dout, ldd,
+                                                   (const T*)y, ldy, scale, shift, part, N, H, W, OH, OW, tiles));
     return YOLO_LAUNCH_CHECK();
 }
 
 template <typename T>
 int launch_stem_conv(const float* img, const void* wp, void* y, int ldy, float* stats, int N, int H, int W, int OH, int OW,
                      int Cout, const float* bias, int act, hipStream_t st) {
-    const long blocks = (long)N * ((OH + 1) / 2) * ((OW + STEM_SEG - 1) / STEM_SEG);
+    const long blocks = stem_tiles(N, OH, OW);
     if (blocks <= 0 || blocks > 0x7fffffffL) return YOLO_ERR_ARG;
-#define STEM_CT(CT) hipLaunchKernelGGL((k_stem_conv<T, CT>), dim3((unsigned)blocks), dim3(256), 0, st, img, (const T*)wp, (T*)y, ldy, stats, N, H, W, OH, OW, Cout, bias, act)
-    switch (Cout / 16) {
-        case 1: STEM_CT(1); break;
-        case 2: STEM_CT(2); break;
-        case 3: STEM_CT(3); break;
-        case 4: STEM_CT(4); break;
-        case 6: STEM_CT(6); break;
-        case 8: STEM_CT(8); break;
-        default: return YOLO_ERR_ARG;
-    }
-#undef STEM_CT
+    STEM_DISPATCH_CT(Cout / 16, hipLaunchKernelGGL((k_stem_conv<T, CT>), dim3((unsigned)blocks), dim3(256), 0, st, img, (const T*)wp, (T*)y,
+                                                   ldy, stats, N, H, W, OH, OW, Cout, bias, act));
     return YOLO_LAUNCH_CHECK();
 }
 
@@ -658,7 +673,7 @@ extern "C" {
 // img: (N,3,H,W) contiguous NCHW of img_dtype; col: [N*OH*OW][32] of col_dtype (an NHWC tensor with C = 32)
 int yolo_stem_im2col(const void* img, int img_dtype, void* col, int col_dtype, int N, int H, int W, int OH, int OW,
                      hipStream_t st) {
-    if (OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return YOLO_ERR_ARG;
+    if (!stem_shape_ok(H, W, OH, OW)) return YOLO_ERR_ARG;
     long total = (long)N * OH * OW;
     int grid = (int)((total + 255) / 256 > 256 * 16 ? 256 * 16 : (total + 255) / 256);
     if (grid < 1) grid = 1;
@@ -690,20 +705,13 @@ int yolo_stem_pack_weights(const void* w, int w_dtype, int Cout, void* out, int 
 // dw32: fp32 (Cout,32,1,1) gradient of the padded 1x1 weights -> dw OIHW (Cout,3,3,3) of dw_dtype
 int yolo_stem_unpack_wgrad(const float* dw32, int Cout, void* dw, int dw_dtype, hipStream_t st) {
     int grid = (Cout * 27 + 255) / 256;
-    switch (dw_dtype) {
-        case YOLO_F32:  hipLaunchKernelGGL((k_stem_unpack_dw<float>), dim3(grid), dim3(256), 0, st, dw32, Cout, (float*)dw); break;
-        case YOLO_BF16: hipLaunchKernelGGL((k_stem_unpack_dw<bf16_t>), dim3(grid), dim3(256), 0, st, dw32, Cout, (bf16_t*)dw); break;
-        case YOLO_F16:  hipLaunchKernelGGL((k_stem_unpack_dw<f16_t>), dim3(grid), dim3(256), 0, st, dw32, Cout, (f16_t*)dw); break;
-        default: return YOLO_ERR_DTYPE;
-    }
+    YOLO_DISPATCH_T(dw_dtype, hipLaunchKernelGGL((k_stem_unpack_dw<T>), dim3(grid), dim3(256), 0, st, dw32, Cout, (T*)dw));
     return YOLO_LAUNCH_CHECK();
 }
 
 // 1 if yolo_stem_conv_fwd handles these arguments (fp32 NCHW image, bf16/f16 compute, Cout in {16,32,48,64,96,128})
 int yolo_stem_conv_eligible(int img_dtype, int dtype, int Cout) {
-    const int ct = Cout / 16;
-    return img_dtype == YOLO_F32 && (dtype == YOLO_BF16 || dtype == YOLO_F16) && Cout % 16 == 0 &&
-           (ct == 1 || ct == 2 || ct == 3 || ct == 4 || ct == 6 || ct == 8);
+    return img_dtype == YOLO_F32 && (dtype == YOLO_BF16 || dtype == YOLO_F16) && Cout % 16 == 0 && stem_ct_ok(Cout / 16);
 }
 
 // y[N][OH][OW][ld >= Cout] (dtype) = conv3x3 stride 2 pad 1 of img (N,3,H,W) fp32 NCHW with wp = yolo_stem_pack_weights
@@ -715,7 +723,7 @@ int yolo_stem_conv_fwd(const float* img, const void* wp, void* y, int ldy, float
     if ((bias != nullptr || act) && stats != nullptr) return YOLO_ERR_ARG;
     if (act != 0 && act != 1) return YOLO_ERR_ARG;
     if (!yolo_stem_conv_eligible(YOLO_F32, dtype, Cout) || ldy < Cout) return YOLO_ERR_ARG;
-    if (OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return YOLO_ERR_ARG;
+    if (!stem_shape_ok(H, W, OH, OW)) return YOLO_ERR_ARG;
     if (dtype == YOLO_BF16) return launch_stem_conv<bf16_t>(img, wp, y, ldy, stats, N, H, W, OH, OW, Cout, bias, act, st);
     return launch_stem_conv<f16_t>(img, wp, y, ldy, stats, N, H, W, OH, OW, Cout, bias, act, st);
 }
@@ -728,18 +736,13 @@ int yolo_stem_wgrad_slabs(void) { return STEM_WG_SLABS; }
 int yolo_stem_wgrad(const float* img, const void* dy, int ldy, float* partial, void* dw, int dw_dtype, int N, int H, int W,
                     int OH, int OW, int Cout, int dtype, hipStream_t st) {
     if (!yolo_stem_conv_eligible(YOLO_F32, dtype, Cout) || ldy < Cout || (ldy & 7) || (reinterpret_cast<uintptr_t>(dy) & 15)) return YOLO_ERR_ARG;
-    if (OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return YOLO_ERR_ARG;
+    if (!stem_shape_ok(H, W, OH, OW)) return YOLO_ERR_ARG;
     int nslab = 0;
     const int rc = dtype == YOLO_BF16 ? launch_stem_wgrad<bf16_t>(img, dy, ldy, partial, N, H, W, OH, OW, Cout, &nslab, st)
                                       : launch_stem_wgrad<f16_t>(img, dy, ldy, partial, N, H, W, OH, OW, Cout, &nslab, st);
     if (rc) return rc;
     const int grid = (Cout * 27 + 7) / 8;
-    switch (dw_dtype) {
-        case YOLO_F32:  hipLaunchKernelGGL((k_stem_wgrad_reduce<float>), dim3(grid), dim3(256), 0, st, partial, nslab, Cout, (float*)dw); break;
-        case YOLO_BF16: hipLaunchKernelGGL((k_stem_wgrad_reduce<bf16_t>), dim3(grid), dim3(256), 0, st, partial, nslab, Cout, (bf16_t*)dw); break;
-        case YOLO_F16:  hipLaunchKernelGGL((k_stem_wgrad_reduce<f16_t>), dim3(grid), dim3(256), 0, st, partial, nslab, Cout, (f16_t*)dw); break;
-        default: return YOLO_ERR_DTYPE;
-    }
+    YOLO_DISPATCH_T(dw_dtype, hipLaunchKernelGGL((k_stem_wgrad_reduce<T>), dim3(grid), dim3(256), 0, st, partial, nslab, Cout, (T*)dw));
     return YOLO_LAUNCH_CHECK();
 }
 
@@ -757,7 +760,7 @@ int yolo_stem_bn_wgrad(const float* img, const void* dout, int ldd, const void* 
     if (!yolo_stem_conv_eligible(YOLO_F32, dtype, Cout) || !pdt_ok(pdt) || (act != 0 && act != 1)) return YOLO_ERR_ARG;
     if (ldd < Cout || (ldd & 7) || (reinterpret_cast<uintptr_t>(dout) & 15)) return YOLO_ERR_ARG;
     if (ldy < Cout || (ldy & 7) || (reinterpret_cast<uintptr_t>(y) & 15)) return YOLO_ERR_ARG;
-    if (OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return YOLO_ERR_ARG;
+    if (!stem_shape_ok(H, W, OH, OW)) return YOLO_ERR_ARG;
     int nslab = 0, rc;
 #define STEM_BW_ACT(T) (act ? launch_stem_bn_wgrad<T, 1>(img, dout, ldd, y, ldy, scale, shift, partial, N, H, W, OH, OW, Cout, &nslab, st) \
                             : launch_stem_bn_wgrad<T, 0>(img, dout, ldd, y, ldy, scale, shift, partial, N, H, W, OH, OW, Cout, &nslab, st))
@@ -765,14 +768,8 @@ int yolo_stem_bn_wgrad(const float* img, const void* dout, int ldd, const void* 
 #undef STEM_BW_ACT
     if (rc) return rc;
     const float count = (float)((long)N * OH * OW);
-#define STEM_BW_FIN(P) hipLaunchKernelGGL((k_stem_bn_wgrad_finalize<P>), dim3(Cout), dim3(1024), 0, st, partial, nslab, Cout, count, gamma, mean, invstd, dgamma, dbeta, (P*)dw, pdt)
-    switch (dw_dtype) {
-        case YOLO_F32:  STEM_BW_FIN(float); break;
-        case YOLO_BF16: STEM_BW_FIN(bf16_t); break;
-        case YOLO_F16:  STEM_BW_FIN(f16_t); break;
-        default: return YOLO_ERR_DTYPE;
-    }
-#undef STEM_BW_FIN
+    YOLO_DISPATCH_T(dw_dtype, hipLaunchKernelGGL((k_stem_bn_wgrad_finalize<T>), dim3(Cout), dim3(1024), 0, st, partial, nslab, Cout, count, gamma,
+                                                 mean, invstd, dgamma, dbeta, (T*)dw, pdt));
     return YOLO_LAUNCH_CHECK();
 }
 
